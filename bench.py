@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """W4A16 GEMM benchmark on MI355X (BASELINE.json: "W4A16 GEMM TOPS vs M, K=N=4096, g=128").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A step = one W4A16 GEMM launch (through the C ABI) at M=512, K=N=4096, group 128 on synthetic data already
 resident in HBM; consecutive steps cycle through enough distinct weight sets to exceed the 256 MiB Infinity
@@ -9,6 +9,11 @@ Cache, so small-M numbers are HBM numbers, not cache numbers.  Rank 0 prints ONE
 
   value / ms_per_step  K steps replayed back to back (one hipGraph), bracketed by barrier + synchronize, max over
                        ranks; includes the launch boundary between consecutive kernels
+
+A plain run measures only that headline step.  --dump-outputs DIR writes what its last timed step computed, y [M, N],
+to DIR/y.npy as float32 (a fixed, seeded sample of rows where y exceeds 60 MiB); the inputs are seeded, so two builds
+can be compared output for output.  --full adds everything below (each figure takes runs of its own):
+
   roofline             the GEMM kernel's OWN duration (hipEvent pair bound to each dispatch, the same clock
                        rocprofv3 --kernel-trace reports) against the HBM or MFMA peak
   sweep                the same two measurements for every M of the BASELINE sweep (1, 8, 64, 512)
@@ -60,6 +65,24 @@ def synthetic_layer(M, K, N, G, seed=0):
     s = rng.uniform(0.005, 0.025, size=(K // G, N)).astype(np.float16)
     x = rng.standard_normal((M, K)).astype(np.float16)
     return x, iw, s, z
+
+
+DUMP_BYTES = 60 << 20      # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """Write each output as <path>/<name>.npy in float32.  Above DUMP_BYTES in all, every array keeps the same fixed, seeded
+    sample of its rows, so that two runs with the same arguments write the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = a.float().cpu().numpy()
+        if total > DUMP_BYTES:
+            keep = max(1, a.shape[0] * DUMP_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        log(f"wrote {os.path.join(path, name + '.npy')}: {a.shape} float32")
 
 
 def pmc_traffic(M, K, N, G, kernel, plan):
@@ -167,18 +190,23 @@ def main():
     ap.add_argument("--K", type=int, default=4096)
     ap.add_argument("--N", type=int, default=4096)
     ap.add_argument("--G", type=int, default=128)
-    ap.add_argument("--sweep", default="1,8,64,512", help="comma-separated M values reported in 'sweep'")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline step's output of the last timed step to DIR/y.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the kernel-only / roofline figures, the M sweep, the layer-shape and prefill legs, the CPU baseline and decode tok/s")
+    ap.add_argument("--sweep", default="1,8,64,512", help="comma-separated M values reported in 'sweep' (--full)")
     ap.add_argument("--sets", type=int, default=0, help="distinct weight sets cycled through (0 = enough for > 320 MiB)")
     ap.add_argument("--kernel", type=int, default=0, help="0 auto, 1 skinny, 2 tiled")
     ap.add_argument("--split-k", type=int, default=0, help="K slices across workgroups (0 = the planner's choice; tuning only)")
     ap.add_argument("--layers", default="1x4096x12288,1x4096x22016,1x11008x4096,16x8192x57344",
-                    help="MxKxN shapes (Llama-2-7B fused qkv, gate_up, down at bs=1; Llama-2-70B gate_up at bs=16) timed kernel-only into 'decode_layers'; '' = none")
+                    help="MxKxN shapes (Llama-2-7B fused qkv, gate_up, down at bs=1; Llama-2-70B gate_up at bs=16) timed kernel-only into 'decode_layers' (--full); '' = none")
     ap.add_argument("--prefill-layers", default="4096x4096x4096,8192x4096x22016,8192x11008x4096,4096x28672x8192",
-                    help="MxKxN prefill-sized launches (K = N = 4096; Llama-2-7B gate_up / down at 8192 tokens; Llama-2-70B down) into 'prefill_layers'; '' = none")
-    ap.add_argument("--cpu-seconds", type=float, default=14.0, help="budget of the cpu_baseline leg (0 = skip)")
+                    help="MxKxN prefill-sized launches (K = N = 4096; Llama-2-7B gate_up / down at 8192 tokens; Llama-2-70B down) into 'prefill_layers' (--full); '' = none")
+    ap.add_argument("--cpu-seconds", type=float, default=14.0, help="budget of the cpu_baseline leg (--full; 0 = skip)")
     ap.add_argument("--decode-seconds", type=float, default=240.0,
-                    help="budget of the decode tok/s leg (Llama-2-7B bs=1,64; Mistral-7B bs=64; Llama-2-70B bs=16; 0 = skip)")
+                    help="budget of the decode tok/s leg (--full; Llama-2-7B bs=1,64; Mistral-7B bs=64; Llama-2-70B bs=16; 0 = skip)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -303,6 +331,15 @@ def main():
         ms_step = replicas.max_over_ranks(dist, e0.elapsed_time(e1) / steps)
         if graph is not None and queued_eager:
             mode = "queued-eager"
+        y_last = y.clone()                       # what the last timed step computed (the kernel-only runs below write y again)
+        res = {"M": M, "ms_per_step": ms_step, "tops": algorithmic_flops(M, K, N) / (ms_step * 1e-3) / 1e12,
+               "launch": mode, "weight_sets_in_timed_region": min(steps, n_sets), "cache_flushed_before_timed_region": True,
+               "clock_warmup_launches_on_other_weight_sets": n_warm,
+               "timed_region": "two hipEvents on the stream around exactly K steps (K <= 256: launches queued behind the untimed ones, "
+                               "K > 256: one hipGraph replay); barrier + synchronize before the untimed launches that precede the first "
+                               "event and after the second event"}
+        if not args.full:
+            return res, y_last
 
         # the kernel's own duration: event pair bound to each dispatch, cycling the same weight sets
         # per-dispatch event pairs: 200 launches whatever --steps says (the mean of 15 separated launches wanders by +-8 % from run
@@ -358,50 +395,52 @@ def main():
         roof["headline_fraction"] = "frac_step"
         roof["frac_clocks"] = {"frac_step": "back-to-back step (graph replay or queued launches), event to event on the stream", "frac": "dispatch duration (event pair = rocprofv3 kernel trace)",
                                "frac_inkernel": "per-wave s_memrealtime stamps, first wave in -> last wave out"}
-        return {"M": M, "ms_per_step": ms_step, "tops": flops / (ms_step * 1e-3) / 1e12, "tops_kernel_only": flops / (k_us * 1e-6) / 1e12,
-                "launch": mode, "weight_sets_in_timed_region": min(steps, n_sets), "cache_flushed_before_timed_region": True,
-                "clock_warmup_launches_on_other_weight_sets": n_warm,
-                "timed_region": "two hipEvents on the stream around exactly K steps (K <= 256: launches queued behind the untimed ones, "
-                                "K > 256: one hipGraph replay); barrier + synchronize before the untimed launches that precede the first "
-                                "event and after the second event",
-                "roofline": roof}, y
+        res.update({"tops_kernel_only": flops / (k_us * 1e-6) / 1e12, "roofline": roof})
+        return res, y_last
 
-    fl = (ctypes.c_float * 60)()
-    lib.quick_amd_dispatch_floor(60, fl, stream.cuda_stream)
-    floor_us = float(np.median(np.asarray(fl[:])[5:]))
-    if rank == 0:
-        log(f"dispatch floor (empty 256x512 kernel, same event-pair clock): {floor_us:.2f} us")
+    if args.full:
+        fl = (ctypes.c_float * 60)()
+        lib.quick_amd_dispatch_floor(60, fl, stream.cuda_stream)
+        floor_us = float(np.median(np.asarray(fl[:])[5:]))
+        if rank == 0:
+            log(f"dispatch floor (empty 256x512 kernel, same event-pair clock): {floor_us:.2f} us")
 
     results = {}
     y_head = None
-    for M in Ms:
+    for M in (Ms if args.full else [args.M]):
         steps = args.steps
         res, y = measure(M, steps, args.warmup)
-        res["roofline"]["empty_kernel_us"] = floor_us
+        if args.full:
+            res["roofline"]["empty_kernel_us"] = floor_us
         results[M] = res
         if M == args.M:
-            y_head = y.clone()
-        if rank == 0:
+            y_head = y
+        if rank == 0 and not args.full:
+            log(f"M={M:4d}  step {res['ms_per_step'] * 1e3:8.2f} us  {res['tops']:8.2f} TOPS")
+        elif rank == 0:
             r = res["roofline"]
             log(f"M={M:4d}  step {res['ms_per_step'] * 1e3:8.2f} us  kernel {r['kernel_us']:8.2f} us (cache-resident "
                 f"{r['kernel_us_cache_resident']:.2f}, in-kernel span {r.get('kernel_us_inkernel', float('nan')):.2f})  {res['tops']:8.2f} TOPS  "
                 f"roofline[{r['bound']}] {r['achieved']:.1f} {r['unit']} = {r['frac'] * 100:.1f}%  (in-kernel {r.get('frac_inkernel', float('nan')) * 100:.1f}%)")
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"y": y_head})
+
     head = results[args.M]
     out = {
-        "metric": "w4a16_gemm_tops", "value": replicas.job_throughput(head["roofline"]["flops"], head["ms_per_step"], world) / 1e12, "unit": "TFLOP/s", "n_gpus": world, "steps": args.steps,
+        "metric": "w4a16_gemm_tops", "value": replicas.job_throughput(algorithmic_flops(args.M, K, N), head["ms_per_step"], world) / 1e12, "unit": "TFLOP/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f16", "data": "synthetic",
         "config": {"workload": f"W4A16 GEMM M={args.M} K={K} N={N} group_size={G} (BASELINE.json configs[1])", "M": args.M, "K": K, "N": N,
                    "group_size": G, "weight_sets_cycled": n_sets, "weight_set_bytes": set_bytes, "launch": head["launch"],
                    "weight_sets_in_timed_region": head["weight_sets_in_timed_region"], "cache_flushed_before_timed_region": True,
                    "parallelism": "replicas only" if world > 1 else "single GPU"},
-        "roofline": head["roofline"],
-        "sweep": [results[m] for m in Ms],
     }
+    if args.full:
+        out.update({"roofline": head["roofline"], "sweep": [results[m] for m in Ms]})
 
     # ---- decode-layer shapes, kernel duration only (HBM-cold: the weight sets cycled exceed the Infinity Cache)
-    if world == 1 and args.layers:
+    if args.full and world == 1 and args.layers:
         out["decode_layers"] = []
         for spec in args.layers.split(","):
             Ml, Kl, Nl = (int(v) for v in spec.lower().split("x"))
@@ -460,7 +499,7 @@ def main():
             log(f"small-M model: {model}")
 
     # ---- prefill-sized launches (compute-bound end of the path), kernel duration only, MFMA roofline
-    if world == 1 and args.prefill_layers:
+    if args.full and world == 1 and args.prefill_layers:
         out["prefill_layers"] = []
         for spec in args.prefill_layers.split(","):
             Ml, Kl, Nl = (int(v) for v in spec.lower().split("x"))
@@ -496,7 +535,7 @@ def main():
             del lsets, larr
 
     # ---- the reference's CPU path on the host cores, bounded sample, rank 0 / N=1 only
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         from oracle import cpu_path
         # host cores actually available to this process (affinity mask and cgroup quota), not the box's core count
         cores = len(os.sched_getaffinity(0))
@@ -570,7 +609,7 @@ def main():
         out["parity_rel_err_vs_cpu_baseline"] = float((y_gpu[:, :n_cpu] - y_cpu.float()).abs().max() / y_cpu.float().abs().max())
 
     # ---- decode tok/s (BASELINE metric, second half), after everything that is timed above
-    if rank == 0 and world == 1 and args.decode_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.decode_seconds > 0:
         try:
             out["decode"] = decode_leg(dev, args.decode_seconds, log)
         except Exception as e:                                   # pragma: no cover  (never lose the GEMM line to the extra leg)

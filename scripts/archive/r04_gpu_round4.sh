@@ -5,7 +5,7 @@ bash scripts/archive/gpu_round.sh r04 > gpurun_out/r04_round.log 2>&1
 out=gpurun_out/r04; mkdir -p $out
 for m in 512 64 8 1; do cp gpurun_out/pmc_r04_m$m/summary.txt $out/pmc_m$m.txt 2>/dev/null; done
 rm -rf gpurun_out/pmc_r04_m*
-timeout 200 python bench.py --steps 2000 --warmup 50 --cpu-seconds 0 --decode-seconds 0 > $out/bench_long.json 2> $out/bench_long.err
+timeout 200 python bench.py --full --steps 2000 --warmup 50 --cpu-seconds 0 --decode-seconds 0 > $out/bench_long.json 2> $out/bench_long.err
 export QUICK_AMD_LIB_OVERRIDE=$PWD/quick_amd/lib/libquick_amd_tools.so
 (
 echo "# per-wave phase stamps (s_memrealtime) and K-loop shader clocks (s_memtime), 8 launches each, HBM-cold weights; 512 x 4096 x 4096"

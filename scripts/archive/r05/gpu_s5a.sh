@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 out=gpurun_out/s5a; mkdir -p $out
 timeout 1500 python -m pytest tests -q -m gpu -x > $out/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $out/pytest_gpu.log
 tail -3 $out/pytest_gpu.log
-timeout 900 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"
+timeout 900 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench rc=$?"
 grep -E "M=|floor|decode" $out/bench_default.err | tail -30
 for spec in "llama2-7b 64" "mistral-7b 64"; do
   set -- $spec

@@ -5,7 +5,7 @@ out=gpurun_out/r06/ab_bench_${AB_TAG:-1}.txt; : > $out
 for r in 1 2; do
 for n in $AB_VARIANTS; do
   if [ $n = base ]; then unset QUICK_AMD_LIB_OVERRIDE; else export QUICK_AMD_LIB_OVERRIDE=$PWD/tools/bin/ab_$n.so; fi
-  timeout 600 python bench.py --cpu-seconds 0 --decode-seconds ${AB_DECODE:-0} --prefill-layers "${AB_PREFILL-}" --layers "${AB_LAYERS:-1x4096x12288,1x4096x22016,1x11008x4096,8x4096x12288,16x4096x22016,16x8192x57344}" 2>/dev/null | tail -1 > /tmp/ab_line.json
+  timeout 600 python bench.py --full --cpu-seconds 0 --decode-seconds ${AB_DECODE:-0} --prefill-layers "${AB_PREFILL-}" --layers "${AB_LAYERS:-1x4096x12288,1x4096x22016,1x11008x4096,8x4096x12288,16x4096x22016,16x8192x57344}" 2>/dev/null | tail -1 > /tmp/ab_line.json
   python - "$n" "$r" >> $out <<'PY'
 import json, sys
 d = json.loads(open("/tmp/ab_line.json").read())

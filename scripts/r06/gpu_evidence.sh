@@ -5,9 +5,9 @@ cd "${GRAFT_REPO_ROOT:-$(pwd)}" || exit 1
 root=$(pwd); out=$root/gpurun_out/r06ev; mkdir -p $out
 (timeout 2400 python -m pytest tests -m gpu -q > $out/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $out/pytest_gpu.log)
 (python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?" >> $out/smoke.log)
-(timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" >> $out/bench.err)
+(timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?" >> $out/bench.err)
 export TMPDIR=/tmp
-(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/rocprof_bench -o bench -- python $root/bench.py --cpu-seconds 0 --decode-seconds 0 > $out/rocprof_bench.json 2> $out/rocprof_bench.err)
+(cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $out/rocprof_bench -o bench -- python $root/bench.py --full --cpu-seconds 0 --decode-seconds 0 > $out/rocprof_bench.json 2> $out/rocprof_bench.err)
 find $out/rocprof_bench -type f ! -name '*kernel_stats.csv' -delete 2>/dev/null
 if [ "$1" != "nopmc" ]; then
   for spec in 1x4096x4096 8x4096x4096 64x4096x4096 512x4096x4096 1x4096x22016 1x11008x4096 16x8192x57344 64x4096x22016 64x4096x12288; do

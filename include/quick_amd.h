@@ -160,15 +160,17 @@ size_t quick_w4a16_workspace_bytes_ex(int M, int K, int N, int group_size, int k
 /* What may be fused around the GEMM (all optional; zero-initialise the struct):
  *   rmsnorm_weight  fp16 [K]: the GEMM consumes RMSNorm(x) * weight (eps = rmsnorm_eps).  Where the kernel holds x whole
  *                   in LDS it normalises there with quick_rmsnorm_f16's rounding points (fp16(fp16(x * rstd) * weight));
- *                   where it takes x fragments straight from L2 it multiplies them by the weight in fp16 and applies
- *                   1 / rms to the fp32 result.  Only where quick_w4a16_can_fuse_rmsnorm() says so (small-M kernels, K not
+ *                   where it takes x fragments straight from L2 (or from a per-wave LDS copy) it sums the rows' squares in
+ *                   a pass in front of the K loop and normalises with the same rounding points (so no product of a massive
+ *                   activation overflows and no row of tiny ones goes subnormal, as x * weight, raw, would).  Only where quick_w4a16_can_fuse_rmsnorm() says so (small-M kernels, K not
  *                   split across workgroups) -- QUICK_ERR_UNSUPPORTED otherwise (run quick_rmsnorm_f16 first).
  *   bias            fp16 [N]      (replaces the torch add of quick/awq/modules/linear/quick.py:165)
  *   residual        fp16 [M, N], may alias y: the decoder block's `hidden + proj(...)`
  *   silu_mul        output channels are gate/up interleaved in blocks of 8 (16t+i gate, 16t+8+i up, i < 8) and the
  *                   epilogue writes y[M, N/2] with y[m, 8t+i] = silu(gate) * up -- the intent of the reference's unused
  *                   QuantFusedMLP (quick/awq/modules/fused/mlp.py:52-71).  Excludes bias and residual.
- * Everything is accumulated in fp32 and rounded to fp16 once (silu_mul rounds gate, up and silu as torch does). */
+ * The product (+ bias) is accumulated in fp32 and rounded to fp16 once; the residual is added to that rounded product and the sum
+ * rounded again -- what GEMM-then-add computes, in every kernel family (silu_mul rounds gate, up and silu as torch does). */
 typedef struct quick_gemm_fusion {
   const void* bias;
   const void* residual;

@@ -199,6 +199,16 @@ __device__ __forceinline__ half_t silu_mul_f16(half_t g, half_t u) {
   return (half_t)((float)(half_t)(x / (1.f + __expf(-x))) * (float)u);
 }
 
+// RMSNorm prologues (fragment and lean flavours): quick_rmsnorm_f16's rounding points on 8 values, fp16(fp16(x * rstd) * weight).  The
+// kernels find 1 / rms of their rows before they multiply anything: |x| * rstd <= sqrt(K) for every element, so no product overflows (a
+// massive activation times its norm weight would, raw) and a row of tiny activations is O(1) before it is rounded (raw, x * weight is subnormal).
+__device__ __forceinline__ half8_t rms_scale8(half8_t x, float rstd, half8_t w) {
+  half8_t o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = (half_t)((half_t)((float)x[j] * rstd) * w[j]);  // cast, then scale: torch order
+  return o;
+}
+
 // wave-uniform values the compiler cannot prove uniform (anything derived from threadIdx)
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 

@@ -208,13 +208,12 @@ __device__ __forceinline__ void skinny_compute_dz(const SkinnyChunk<NTW, GM, U, 
 // biased8's order) -- so an accumulator lane ends up with A (even channel lane) or C (odd channel lane) of its 4 tokens
 // and gets the other from its neighbour with one DPP move.  ~12 VALU per unit per wave on top of 5 per packed dword and
 // ~12 per (unit, channel tile); no table, no LDS, no per-workgroup prologue.
-// LN: RMSNorm folded in -- the x fragments are multiplied by the norm weight in registers (fp16, like the weight multiply of
-// quick_rmsnorm_f16), the squares of the raw x are summed per lane (`ssq`), and the row scale 1/rms is applied to the
-// fp32 result in skinny_finish: gemm(x * w) * rstd instead of gemm(fp16(fp16(x * rstd) * w)).
+// LN: RMSNorm folded in -- the kernel sums the squares of its rows in a pass over x in front of the loop, and the x fragments
+// are normalised in registers with quick_rmsnorm_f16's rounding points (rms_scale8: fp16(fp16(x * rstd) * w)).
 template <int NTW, int GM, int U, bool LN = false>
 __device__ __forceinline__ void skinny_compute_dzf(const SkinnyChunk<NTW, GM, U, false, LN>& c, int kt, int kt_end,
                                                    half8_t bconst, bool odd, floatx4 (&acc)[NTW],
-                                                   float* ssq = nullptr) {
+                                                   float rstd = 0.f) {
   constexpr int NG = groups_per_tile<GM>();  // units per 128-k tile
   constexpr int TPU = 4 / NG;                // k-steps per unit
 #pragma unroll
@@ -224,13 +223,7 @@ __device__ __forceinline__ void skinny_compute_dzf(const SkinnyChunk<NTW, GM, U,
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         if constexpr (LN) {
-          xs[t] = c.xf[u][t] * c.gf[u][t];
-          const u32x4 raw = __builtin_bit_cast(u32x4, c.xf[u][t]);
-#pragma unroll
-          for (int d = 0; d < 4; ++d) {
-            const uint32_t rd = raw[d];
-            *ssq = __builtin_amdgcn_fdot2(as_h2(rd), as_h2(rd), *ssq, false);
-          }
+          xs[t] = rms_scale8(c.xf[u][t], rstd, c.gf[u][t]);
         } else {
           xs[t] = c.xf[u][t];
         }
@@ -281,16 +274,10 @@ __device__ __forceinline__ void skinny_compute_dzf(const SkinnyChunk<NTW, GM, U,
 // TR: the accumulators come from the deferred-zero path (lane = channel n16, registers = tokens 4q..4q+3) and are
 // written to LDS transposed, so that everything after the barrier sees the usual fragment (lane = token, registers =
 // channels 4q..4q+3).
-template <int NTW, int WAVES, bool TR, bool LN = false>
+template <int NTW, int WAVES, bool TR>
 __device__ __forceinline__ void skinny_finish(const GemmArgs& a, floatx4 (&acc)[NTW], floatx4* red, char* smem, int nb,
-                                              int nblocks, int mb, int ks, int lane, int wave, float ssq = 0.f) {
+                                              int nblocks, int mb, int ks, int lane, int wave) {
   const int n16 = lane & 15, q = lane >> 4;
-  float* ssq_lds = (float*)(red + WAVES * NTW * 64);  // LN: [WAVES][16] behind the reduction buffer
-  if constexpr (LN) {  // this wave's sum of squares per token: the 4 k-octet lanes of a token row, then LDS
-    ssq += __shfl_xor(ssq, 16);
-    ssq += __shfl_xor(ssq, 32);
-    if (q == 0) ssq_lds[wave * 16 + n16] = ssq;
-  }
   if constexpr (TR && NTW == 1) {
     if (a.ksplit == 1) {
       // Deferred-zero path, K not split across workgroups: every wave finishes its own 16 / WAVES tokens (lane = one
@@ -317,8 +304,9 @@ __device__ __forceinline__ void skinny_finish(const GemmArgs& a, floatx4 (&acc)[
       if (live) {
         const int n = nb * 16 + n16;
         if (a.bias) v += (float)a.bias[n];
-        if (a.residual) v += (float)a.residual[(size_t)m * a.N + n];
-        a.Y[(size_t)m * a.N + n] = (half_t)v;
+        half_t o = (half_t)v;  // the residual joins the ROUNDED product, as GEMM-then-add does
+        if (a.residual) o = (half_t)((float)o + (float)a.residual[(size_t)m * a.N + n]);
+        a.Y[(size_t)m * a.N + n] = o;
       }
       return;
     }
@@ -357,14 +345,6 @@ __device__ __forceinline__ void skinny_finish(const GemmArgs& a, floatx4 (&acc)[
   }
   if (wave >= NTW) return;
   const int m = mb * 16 + n16;
-  if constexpr (LN) {  // lane = token n16: scale its 4 channels by 1 / rms(x[token])
-    float ss = 0.f;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) ss += ssq_lds[w * 16 + n16];
-    const float rstd = rsqrtf(ss / (float)a.K + a.ln_eps);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) sum[r] *= rstd;
-  }
   if (a.silu_mul) {
     floatx4 up;
 #pragma unroll
@@ -384,14 +364,14 @@ __device__ __forceinline__ void skinny_finish(const GemmArgs& a, floatx4 (&acc)[
 #pragma unroll
       for (int r = 0; r < 4; ++r) sum[r] += (float)b[r];
     }
-    if (a.residual) {
-      const half4_t b = *(const half4_t*)(a.residual + (size_t)m * a.N + nc);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) sum[r] += (float)b[r];
-    }
     half4_t o;
 #pragma unroll
     for (int r = 0; r < 4; ++r) o[r] = (half_t)sum[r];
+    if (a.residual) {  // added to the ROUNDED product, as GEMM-then-add does
+      const half4_t b = *(const half4_t*)(a.residual + (size_t)m * a.N + nc);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = (half_t)((float)o[r] + (float)b[r]);
+    }
     *(half4_t*)(a.Y + (size_t)m * a.N + nc) = o;
   }
 }
@@ -480,7 +460,6 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_skinny_kernel(const GemmArgs
 
   SkinnyChunk<NTW, GM, U, XLDS, LN> cA, cB;
   if constexpr (!PERSIST) {
-    float ssq = 0.f;
     const half_t* gp = LN ? a.ln_w + q * 8 : nullptr;
     // one block per workgroup, x fragments straight from L2
     const int cb = bx * NTW;
@@ -498,6 +477,31 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_skinny_kernel(const GemmArgs
     // been through the parity suite in this exact form since r01.
     if (kt_begin < kt_end) skinny_load<NTW, GM, U, XLDS, LN, NT>(cA, kt_begin, kt_end - 1, bufs, cb, xp, a, gp);
     __builtin_amdgcn_sched_barrier(0);
+    // LN: 1 / rms of every row before the first chunk is computed -- the first chunk's weights (and x, norm weight fragments) are
+    // already on their way: each wave sums the squares of its k tiles of the rows (the fragments the loop reads, lane = row n16;
+    // two tiles' requests in flight at a time), the sums meet in LDS behind the reduction buffer, one barrier
+    float rstd = 0.f;
+    if constexpr (LN) {
+      float ss = 0.f;
+#pragma unroll 2
+      for (int kt = kt_begin; kt < kt_end; ++kt) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const u32x4 v = *(const u32x4*)(xp + kt * 128 + 32 * t);
+#pragma unroll
+          for (int d = 0; d < 4; ++d) ss = __builtin_amdgcn_fdot2(as_h2(v[d]), as_h2(v[d]), ss, false);
+        }
+      }
+      ss += __shfl_xor(ss, 16);
+      ss += __shfl_xor(ss, 32);
+      float* ssq_lds = (float*)(red + WAVES * NTW * 64);
+      if (q == 0) ssq_lds[wave * 16 + n16] = ss;
+      __syncthreads();
+      float st = 0.f;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) st += ssq_lds[w * 16 + n16];
+      rstd = rsqrtf(st / (float)a.K + a.ln_eps);
+    }
 #ifdef QA_EXP_SKINNY_UNCOND   // (A/B builds only: the unconditional requests of profiles/r05_skinny_variants.txt -- wrong results in the four-tile build)
 #define QA_SKINNY_IF(c)
 #else
@@ -512,17 +516,17 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_skinny_kernel(const GemmArgs
       QA_SKINNY_IF(kt + U < kt_end) skinny_load<NTW, GM, U, XLDS, LN, NT>(cB, kt + U, kt_end - 1, bufs, cb, xp, a, gp);
       __builtin_amdgcn_sched_barrier(0);
       QA_SKINNY_FULLWAIT(0);
-      if constexpr (DZ) skinny_compute_dzf<NTW, GM, U, LN>(cA, kt, kt_end, bconst, (lane & 1) != 0, acc, &ssq);
+      if constexpr (DZ) skinny_compute_dzf<NTW, GM, U, LN>(cA, kt, kt_end, bconst, (lane & 1) != 0, acc, rstd);
       else skinny_compute<NTW, GM, U, XLDS>(cA, kt, kt_end, nullptr, acc);
       if (kt + U >= kt_end) break;
       QA_SKINNY_IF(kt + 2 * U < kt_end) skinny_load<NTW, GM, U, XLDS, LN, NT>(cA, kt + 2 * U, kt_end - 1, bufs, cb, xp, a, gp);
       __builtin_amdgcn_sched_barrier(0);
       QA_SKINNY_FULLWAIT(1);
-      if constexpr (DZ) skinny_compute_dzf<NTW, GM, U, LN>(cB, kt + U, kt_end, bconst, (lane & 1) != 0, acc, &ssq);
+      if constexpr (DZ) skinny_compute_dzf<NTW, GM, U, LN>(cB, kt + U, kt_end, bconst, (lane & 1) != 0, acc, rstd);
       else skinny_compute<NTW, GM, U, XLDS>(cB, kt + U, kt_end, nullptr, acc);
     }
     QA_SKINNY_FULLWAIT(3);
-    skinny_finish<NTW, WAVES, DZ, LN>(a, acc, red, smem, bx, nblocks, mb, ks, lane, wave, ssq);
+    skinny_finish<NTW, WAVES, DZ>(a, acc, red, smem, bx, nblocks, mb, ks, lane, wave);
     if constexpr (SPAN) span_stamp(a.span, 1);
     return;
   }
@@ -947,11 +951,14 @@ __global__ __launch_bounds__(64 * WN * WK) void w4a16_tiled_kernel(const GemmArg
       for (int mt = 0; mt < BMT; ++mt) {
         const int m = m0 + mt * 16 + n16;
         if (m < a.M) {
-          half4_t res = {(half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
-          if (a.residual) res = *(const half4_t*)(a.residual + (size_t)m * a.N + nc);
           half4_t o;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = (half_t)(acc[j][mt][r] + (float)b[r] + (float)res[r]);
+          for (int r = 0; r < 4; ++r) o[r] = (half_t)(acc[j][mt][r] + (float)b[r]);
+          if (a.residual) {  // added to the ROUNDED product, as GEMM-then-add does
+            const half4_t res = *(const half4_t*)(a.residual + (size_t)m * a.N + nc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[r] = (half_t)((float)o[r] + (float)res[r]);
+          }
           *(half4_t*)(a.Y + (size_t)m * a.N + nc) = o;
         }
       }
@@ -1126,7 +1133,7 @@ __global__ __launch_bounds__(512) void w4a16_frag8_kernel(const GemmArgs a) {
     __builtin_amdgcn_sched_barrier(0);
     skinny_compute_dzf<NTW, 0, 1, false>(c[i & 1], 0, 1, bconst, (lane & 1) != 0, acc);   // (kt = 0 < kt_end = 1: the k tile is always this wave's)
   }
-  skinny_finish<NTW, WAVES, true, false>(a, acc, red, smem, bx, nblocks, mb, ks, lane, wave);
+  skinny_finish<NTW, WAVES, true>(a, acc, red, smem, bx, nblocks, mb, ks, lane, wave);
   if constexpr (SPAN) span_stamp(a.span, 1);
 }
 
@@ -2508,10 +2515,11 @@ int quick_w4a16_can_fuse_rmsnorm(int M, int K, int N, int group_size) {
   // the deferred-zero skinny kernel copies (and tabulates) x per workgroup anyway: normalising on the way costs a
   // second pass over LDS, not a launch
   const Plan p = make_plan(M, K, N, group_size, QUICK_KERNEL_AUTO, 0);
-  if (p.kernel == QUICK_KERNEL_LEAN) return p.lean_tmax > 0;   // x * weight in LDS on the way in, 1 / rms on the fp32 result
+  if (p.kernel == QUICK_KERNEL_LEAN) return p.lean_tmax > 0;   // sums of squares of the LDS copy, one barrier, x normalised in LDS
   if (!(p.kernel == QUICK_KERNEL_SKINNY && p.dz && p.ksplit == 1 && !p.frag8_t && (p.xlds || (p.mt >= 2 && p.waves == 8)))) return 0;
-  // The fragment flavour pays for the norm in registers (188 against 134, the weight multiply and the squares on every x fragment of every
-  // channel block): on a very large layer that is more than a separate launch of quick_rmsnorm_f16.  Llama-2-70B at bs = 16, one-session
+  // The fragment flavour pays for the norm in registers (a pass over x for the sums of squares in front of the loop, the normalisation
+  // fp16(fp16(x * rstd) * w) on every x fragment of every channel block; the bound below was measured with r05's construction, x * w in
+  // fp16 and the squares on every fragment): on a very large layer that is more than a separate launch of quick_rmsnorm_f16.  Llama-2-70B at bs = 16, one-session
   // A/B (profiles/r05_decode70_ab.txt): gate_up (8192 x 57344) un-fused 1412 -> 1456 tok/s, every fragment launch un-fused 1426; Mistral-7B's
   // 4096 x 28672 at bs = 32 LOSES 2 % un-fused.  So: fused up to K * N = 2^28.  QUICK_AMD_LN_FRAGMENT_MAX overrides the bound (A/B; 0 = never fuse).
   static const long ln_fragment_max = [] {

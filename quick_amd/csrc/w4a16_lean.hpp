@@ -18,8 +18,9 @@
 //     the chip's memory-level parallelism comes from several small workgroups per CU, not from a ring inside one;
 //   * one barrier, in front of the reduction.
 //
-// G % 128 == 0.  RMSNorm prologue: x * weight in fp16 on the way (in LDS), 1 / rms on the fp32 result -- the rounding points of the
-// fragment flavour (w4a16_gemm.hip, skinny_compute_dzf LN).  Epilogues: bias, residual, SiLU * mul as in skinny_finish.
+// G % 128 == 0.  RMSNorm prologue: the rows' sums of squares from the LDS copy of x (one barrier), then x normalised in place with
+// quick_rmsnorm_f16's rounding points, fp16(fp16(x * rstd) * weight) (rms_scale8, as the fragment flavour of w4a16_gemm.hip).
+// Epilogues: bias, residual (added to the rounded product), SiLU * mul as in skinny_finish.
 #pragma once
 #include "w4a16_args.hpp"
 
@@ -210,7 +211,67 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_lean_kernel(const half_t* __
   constexpr int SMR = MR == 16 ? 1 : MR;
   floatx4 sm[MR == 16 ? TMAX : 1];
   float sA[MR == 16 ? 1 : TMAX][SMR], sC[MR == 16 ? 1 : TMAX][SMR];
-  floatx4 sq = floatx4{0.f, 0.f, 0.f, 0.f};
+  // RMSNorm: 1 / rms of every token before anything is multiplied: the squares of this wave's k tiles, summed over the waves in LDS behind
+  // one barrier; then the wave normalises its own k range of x in place with quick_rmsnorm_f16's rounding points (rms_scale8) -- everything
+  // that reads fragments reads normalised x.  MR = 16: lane = token n16, as the fragment reads, in a pass of its own; MR = 1, 4: lane-linear
+  // on the compact copy (lane = 8 consecutive k of one token), inside the unit-sum pass below -- all 64 lanes busy at 1..4 tokens
+  [[maybe_unused]] float rstd_t[SMR];
+  if constexpr (LN) {
+    float* sqp = (float*)(smem + ssq_off);
+    if constexpr (MR == 16) {
+      float ss = 0.f;
+      for (int j = 0; j < T; ++j) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const u32x4 v = *(const u32x4*)(xl + (unsigned)(kb + j) * 256u + 64 * t);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) ss = __builtin_amdgcn_fdot2(as_h2(v[i]), as_h2(v[i]), ss, false);
+        }
+      }
+      ss += __shfl_xor(ss, 16);
+      ss += __shfl_xor(ss, 32);
+      if (q == 0) sqp[wave * 16 + n16] = ss;
+    } else {
+#pragma unroll
+      for (int tk = 0; tk < SMR; ++tk) {
+        float ss = 0.f;
+#pragma unroll
+        for (int sg = 0; sg < NSZ; ++sg) {
+          const unsigned cb = (unsigned)(kb * 128 + 512 * sg) * 2u + (unsigned)lane * 16u;
+          if (lane < 16 * (T - 4 * sg) && tk < rows) {
+            const u32x4 v = *(const u32x4*)(smem + x_off + (unsigned)tk * pitch + cb);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ss = __builtin_amdgcn_fdot2(as_h2(v[i]), as_h2(v[i]), ss, false);
+          }
+        }
+        ss = wave_sum(ss);
+        if (lane == 0) sqp[wave * 16 + tk] = ss;
+      }
+    }
+    __syncthreads();
+    const auto rstd_of = [&](int tok) __attribute__((always_inline)) {
+      float st = 0.f;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) st += sqp[w * 16 + tok];
+      return rsqrtf(st / (float)aK + rest.ln_eps);
+    };
+    if constexpr (MR == 16) {
+      const float rstd = rstd_of(n16);
+      if (n16 < rows) {  // (lanes of the replayed rows past M read the last row: they must not write it twice)
+        for (int j = 0; j < T; ++j) {
+          const unsigned ko = (unsigned)(kb + j) * 256u;
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            half8_t* p = (half8_t*)(xl + ko + 64 * t);
+            *p = rms_scale8(*p, rstd, *(const half8_t*)(gl + ko + 64 * t));
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int tk = 0; tk < SMR; ++tk) rstd_t[tk] = rstd_of(min(tk, rows - 1));   // (normalised in the unit-sum pass below)
+    }
+  }
   if constexpr (MR == 16) {
 #pragma unroll
     for (int j = 0; j < TMAX; ++j) {
@@ -220,45 +281,21 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_lean_kernel(const half_t* __
         half8_t xf[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) xf[t] = *(const half8_t*)(xl + ko + 64 * t);
-        if constexpr (LN) {
-          // RMSNorm: sum of squares of the raw x as the diagonal of x x^T; x * weight in fp16 (nothing is written back: the tile loop below
-          // multiplies again -- an in-place update chains every tile's reads behind the previous tile's writes)
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            const half8_t gf = *(const half8_t*)(gl + ko + 64 * t);
-            sq = mfma16(xf[t], xf[t], sq);
-            xf[t] = xf[t] * gf;
-          }
-        }
 #pragma unroll
         for (int t = 0; t < 4; ++t) sm[j] = mfma16(xf[t], bconst, sm[j]);
       }
     }
-    if constexpr (LN) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (n16 == 4 * q + r) ((float*)(smem + ssq_off))[wave * 16 + n16] = sq[r];
-    }
   } else {
-    float ss[SMR];
-#pragma unroll
-    for (int tk = 0; tk < SMR; ++tk) ss[tk] = 0.f;
 #pragma unroll
     for (int sg = 0; sg < NSZ; ++sg) {
       const bool mine = lane < 16 * (T - 4 * sg);
       const unsigned cb = (unsigned)(kb * 128 + 512 * sg) * 2u + (unsigned)lane * 16u;
-      u32x4 gv = u32x4{0u, 0u, 0u, 0u};
-      if constexpr (LN) gv = mine ? *(const u32x4*)(smem + lnw_off + cb) : gv;
 #pragma unroll
       for (int tk = 0; tk < SMR; ++tk) {
         char* xp = smem + x_off + (unsigned)min(tk, rows - 1) * pitch + cb;  // (tokens past M: the last one again, never stored)
         u32x4 v = mine ? *(const u32x4*)xp : u32x4{0u, 0u, 0u, 0u};
-        if constexpr (LN) {
-          // RMSNorm: x * weight in fp16 back into the compact copy (lane-linear, before any fragment of it is read), squares summed per lane
-#pragma unroll
-          for (int i = 0; i < 4; ++i) ss[tk] = __builtin_amdgcn_fdot2(as_h2(v[i]), as_h2(v[i]), ss[tk], false);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) v[i] = as_u32(as_h2(v[i]) * as_h2(gv[i]));
+        if constexpr (LN) {   // normalised back into the compact copy (lane-linear, before any fragment of it is read)
+          v = __builtin_bit_cast(u32x4, rms_scale8(__builtin_bit_cast(half8_t, v), rstd_t[tk], *(const half8_t*)(smem + lnw_off + cb)));
           if (mine && tk < rows) *(u32x4*)xp = v;
         }
         const half2_t one2 = {(half_t)1.f, (half_t)1.f};
@@ -272,13 +309,6 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_lean_kernel(const half_t* __
             sA[4 * sg + qq][tk] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sa), 16 * qq));
             sC[4 * sg + qq][tk] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, sc), 16 * qq));
           }
-      }
-    }
-    if constexpr (LN) {
-#pragma unroll
-      for (int tk = 0; tk < SMR; ++tk) {
-        const float tot = wave_sum(ss[tk]);
-        if (lane == 0) ((float*)(smem + ssq_off))[wave * 16 + tk] = tot;
       }
     }
   }
@@ -304,10 +334,6 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_lean_kernel(const half_t* __
         half8_t xf[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) xf[t] = *(const half8_t*)(xl + ko + 64 * t);
-        if constexpr (LN && MR == 16) {
-#pragma unroll
-          for (int t = 0; t < 4; ++t) xf[t] = xf[t] * *(const half8_t*)(gl + ko + 64 * t);
-        }
         floatx4 xa, nc;
         if constexpr (MR == 16) {
 #pragma unroll
@@ -364,16 +390,6 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_lean_kernel(const half_t* __
 #pragma unroll
       for (int w = 1; w < WAVES; ++w) sum += red[(w * NTW + ct) * 64 + lane];
       // lane (n16, q) holds tokens 4q .. 4q+3 of channel n16
-      if constexpr (LN) {
-        const float* sqp = (const float*)(smem + ssq_off);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float ss = 0.f;
-#pragma unroll
-          for (int w = 0; w < WAVES; ++w) ss += sqp[w * 16 + 4 * q + r];
-          sum[r] *= rsqrtf(ss / (float)aK + rest.ln_eps);
-        }
-      }
       const int nt = blk * NTW + ct, n = nt * 16 + n16;
       if (rest.silu_mul) {
 #pragma unroll
@@ -388,15 +404,14 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_lean_kernel(const half_t* __
         for (int r = 0; r < 4; ++r) {
           const int m = row0 + 4 * q + r;
           if (4 * q + r < rows) {
-            float v = sum[r] + bv;
-            if (rest.residual) v += (float)rest.residual[(size_t)m * aN + n];
+            half_t hv = (half_t)(sum[r] + bv);
+            if (rest.residual) hv = (half_t)((float)hv + (float)rest.residual[(size_t)m * aN + n]);   // to the ROUNDED product, as GEMM-then-add
 #ifdef QA_EXP_LEAN_OVERLAP
             if (rest.signal != nullptr) {   // rows written THROUGH to memory (sc1): the successor on another XCD asks for them with sc1 loads, no cache-wide fence on either side
-              const half_t hv = (half_t)v;
               asm volatile("global_store_short %0, %1, off sc0 sc1" ::"v"(rest.Y + (size_t)m * aN + n), "v"((unsigned)__builtin_bit_cast(unsigned short, hv)) : "memory");
             } else
 #endif
-            rest.Y[(size_t)m * aN + n] = (half_t)v;
+            rest.Y[(size_t)m * aN + n] = hv;
           }
         }
       }

@@ -16,7 +16,8 @@
 //
 // After the loop the eight partial tiles meet in LDS (fp32, summed in wave order: results do not depend on timing): wave w finishes
 // register pair w of every 32 x 32 tile -- channels 8 (w / 2) + 4 h + 2 (w % 2) + {0, 1} of the pair (SiLU * mul: registers j and j + 4,
-// gate and up of one output channel).  Epilogues as the lean kernels: bias and residual in fp32 before the one rounding, SiLU * mul.
+// gate and up of one output channel).  Epilogues as the lean kernels: bias in fp32 before the product's one rounding, the residual added to the rounded product
+// (GEMM-then-add), SiLU * mul.
 #pragma once
 #include "w4a16_args.hpp"
 #ifdef QA_XM_LOOP_INC   // (timing experiments: a loop file written by XM_EXP=<n> tools/gen_xm_loop.py, wrong results)
@@ -112,12 +113,12 @@ __device__ __forceinline__ void xm_finish(const floatx16 (&accr)[MB * PR], char*
             v0 += (float)bv[0];
             v1 += (float)bv[1];
           }
-          if (rest.residual) {
+          half2_t o = half2_t{(half_t)v0, (half_t)v1};
+          if (rest.residual) {  // added to the ROUNDED product, as GEMM-then-add does
             const half2_t rv = *(const half2_t*)(rest.residual + (size_t)m * aN + n);
-            v0 += (float)rv[0];
-            v1 += (float)rv[1];
+            o = half2_t{(half_t)((float)o[0] + (float)rv[0]), (half_t)((float)o[1] + (float)rv[1])};
           }
-          *(half2_t*)(rest.Y + (size_t)m * aN + n) = half2_t{(half_t)v0, (half_t)v1};
+          *(half2_t*)(rest.Y + (size_t)m * aN + n) = o;
         }
       }
     }

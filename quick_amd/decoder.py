@@ -202,6 +202,28 @@ def decode_step_fused(model: SyntheticDecoder, tok, pos):
 
 
 @torch.no_grad()
+def torch_decode_hidden(model, tok, pos, mask):
+    """SyntheticDecoder.forward for T = 1 in torch ops (the tests' reference for decode_step_fused), returning the final normed hidden state
+    instead of the argmax."""
+    cfg, B = model.cfg, tok.shape[0]
+    H, nh, nkv, D = cfg.hidden, cfg.heads, cfg.kv_heads, cfg.head_dim
+    x = model.embed[tok]
+    cos, sin = model.cos.index_select(0, pos), model.sin.index_select(0, pos)
+    for l in model.layers:
+        h = _rms_norm(x, l["ln1"])
+        q, k, v = l["qkv"](h).split((H, nkv * D, nkv * D), dim=-1)
+        q = _rope(q.view(B, 1, nh, D).transpose(1, 2), cos, sin)
+        k = _rope(k.view(B, 1, nkv, D).transpose(1, 2), cos, sin)
+        l["k"].index_copy_(2, pos, k)
+        l["v"].index_copy_(2, pos, v.view(B, 1, nkv, D).transpose(1, 2))
+        att = F.scaled_dot_product_attention(q, l["k"], l["v"], attn_mask=mask, enable_gqa=nkv != nh)
+        x = x + l["o"](att.transpose(1, 2).reshape(B, 1, H))
+        gu = l["gate_up"](_rms_norm(x, l["ln2"])).view(B, 1, cfg.intermediate // 8, 2, 8)
+        x = x + l["down"](F.silu(gu[..., 0, :].reshape(B, 1, -1)) * gu[..., 1, :].reshape(B, 1, -1))
+    return _rms_norm(x[:, -1], model.norm)
+
+
+@torch.no_grad()
 def run_generation(model: SyntheticDecoder, ctx, n_generate, use_graph=True, fused=True):
     """examples/benchmark.py:38-67 methodology: events around every forward; prefill = iteration 0, decode = the rest.
     Returns (prefill_seconds, [decode step seconds])."""

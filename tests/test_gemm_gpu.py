@@ -794,9 +794,8 @@ def test_decode_glue_kernels_against_torch(qa, device):
                                      (16, 8192, 10240, 256)])
 def test_rmsnorm_prologue_matches_two_launches(qa, device, M, K, N, G):
     """gemm(rmsnorm(x) * w) in one launch.  Table flavour (x in LDS): the prologue reproduces quick_rmsnorm_f16's rounding
-    points, the only difference to the two-launch result is the summation order of the squares.  Fragment flavour (the
-    last four shapes): x * w in fp16 on the fragments, 1 / rms applied to the fp32 result -- other rounding points, same
-    tolerance."""
+    points, the only difference to the two-launch result is the summation order of the squares.  Fragment and lean flavours:
+    the same rounding points, the squares summed in a pass in front of the K loop."""
     from quick_amd import kernels as K_
     x, iw, s, z = oracle.make_synthetic(M, K, N, G, seed=M + K + N)
     packed = _pack_dev(iw, s, z, device)
@@ -929,25 +928,8 @@ def test_lm_head_argmax_against_torch(qa, device, B, V, H, norm):
 
 
 def _torch_decode_hidden(model, tok, pos, mask):
-    """SyntheticDecoder.forward for T = 1, returning the final normed hidden state instead of the argmax."""
-    import torch.nn.functional as F
-    from quick_amd.decoder import _rms_norm, _rope
-    cfg, B = model.cfg, tok.shape[0]
-    H, nh, nkv, D = cfg.hidden, cfg.heads, cfg.kv_heads, cfg.head_dim
-    x = model.embed[tok]
-    cos, sin = model.cos.index_select(0, pos), model.sin.index_select(0, pos)
-    for l in model.layers:
-        h = _rms_norm(x, l["ln1"])
-        q, k, v = l["qkv"](h).split((H, nkv * D, nkv * D), dim=-1)
-        q = _rope(q.view(B, 1, nh, D).transpose(1, 2), cos, sin)
-        k = _rope(k.view(B, 1, nkv, D).transpose(1, 2), cos, sin)
-        l["k"].index_copy_(2, pos, k)
-        l["v"].index_copy_(2, pos, v.view(B, 1, nkv, D).transpose(1, 2))
-        att = F.scaled_dot_product_attention(q, l["k"], l["v"], attn_mask=mask, enable_gqa=nkv != nh)
-        x = x + l["o"](att.transpose(1, 2).reshape(B, 1, H))
-        gu = l["gate_up"](_rms_norm(x, l["ln2"])).view(B, 1, cfg.intermediate // 8, 2, 8)
-        x = x + l["down"](F.silu(gu[..., 0, :].reshape(B, 1, -1)) * gu[..., 1, :].reshape(B, 1, -1))
-    return _rms_norm(x[:, -1], model.norm)
+    from quick_amd.decoder import torch_decode_hidden
+    return torch_decode_hidden(model, tok, pos, mask)
 
 
 @pytest.mark.parametrize("K,N", [(8192, 10240), (8192, 57344), (28672, 8192)])
@@ -1269,7 +1251,7 @@ def test_forced_four_wave_id_with_half_a_256_channel_tile(qa, device, kid):
 def test_eight_tile_fragment_kernel_against_oracle(qa, device, M, K, N, ks):
     """[r05] w4a16_frag8_kernel -- eight channel tiles per workgroup, straight-line, every wave exactly T k tiles -- forced by kernel id
     (SKINNY, 8 tiles) over every T it is built for and 1 / 2 / 4 K slices: against the oracle into a NaN-poisoned output, three times
-    (the loop form of this instantiation failed from run to run), with bias + residual (fp32 adds, one rounding, as the four-tile kernel), and SiLU * mul."""
+    (the loop form of this instantiation failed from run to run), with bias + residual (bias before the product's rounding, the residual after it, as the four-tile kernel), and SiLU * mul."""
     from quick_amd import kernels as K_
     kid = K_.KERNEL_SKINNY | (8 << 4)
     plan = K_.plan_describe(M, K, N, 128, kid, ks)
@@ -1288,7 +1270,7 @@ def test_eight_tile_fragment_kernel_against_oracle(qa, device, M, K, N, ks):
     assert rel_err(ys[0].cpu().numpy(), y4.float().cpu().numpy()) <= 1e-3
     bias = torch.linspace(-1, 1, N, device=device).half()
     res = torch.randn(M, N, device=device).half()
-    yb = qa.gemm_forward(xd, *packed, bias=bias, residual=res, kernel_id=kid, grid_split_k=ks)   # (fp32 adds, one rounding: skinny_finish)
+    yb = qa.gemm_forward(xd, *packed, bias=bias, residual=res, kernel_id=kid, grid_split_k=ks)   # (skinny_finish: GEMM-then-add rounding)
     assert rel_err(yb.cpu().numpy(), want + bias.float().cpu().numpy() + res.float().cpu().numpy()) <= TOL, plan
     assert torch.equal(yb, qa.gemm_forward(xd, *packed, bias=bias, residual=res, kernel_id=K_.KERNEL_SKINNY | (4 << 4) | (2 << 8), grid_split_k=ks)) or \
         rel_err(yb.cpu().numpy(), qa.gemm_forward(xd, *packed, bias=bias, residual=res, kernel_id=K_.KERNEL_SKINNY | (4 << 4) | (2 << 8)).float().cpu().numpy()) <= 1e-3

@@ -1,4 +1,4 @@
-// Host-side interface of the mid-token kernels' translation unit (w4a16_xm.hip) for the planner / dispatcher in w4a16_gemm.hip.
+// Host-side interface of the mid-token kernels' translation unit (w4a16_xm.hip) for the planner (w4a16_plan.hip) and the dispatcher (w4a16_gemm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

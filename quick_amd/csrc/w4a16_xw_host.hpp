@@ -1,4 +1,4 @@
-// Host-side interface of the 128 x 256 four-wave kernels' translation unit (w4a16_xw.hip) for the planner / dispatcher in w4a16_gemm.hip.
+// Host-side interface of the 128 x 256 four-wave kernels' translation unit (w4a16_xw.hip) for the planner (w4a16_plan.hip) and the dispatcher (w4a16_gemm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -294,7 +294,7 @@ def test_plan_describe_pins_the_shape_heuristics():
     # [r05] 9..16 tokens on the Llama-2-70B layers: the straight-line eight-tile fragment kernel where K / 128 = 8 waves x slices x {2, 4, 7, 8} and the
     # blocks come in multiples of 64 (measured ahead there); 80 blocks (the fused qkv) stay with four tiles
     # [r06, late] ... with SEVEN tiles per workgroup where that makes fuller rounds of one workgroup per CU: 57344 = 448 blocks of 128 (1.75 rounds) = 512 of 112 (two),
-    # 28672 = 224 of 128 = 256 of 112 (every CU busy); QUICK_AMD_FRAG7=0 / the forced eight-tile id keep eight
+    # 28672 = 224 of 128 = 256 of 112 (every CU busy); the forced eight-tile id keeps eight
     assert plan(16, 8192, 57344).startswith("skinny ntw=7") and "grid=512x1x1 ksplit=1" in plan(16, 8192, 57344)
     assert "grid=448x1x1 ksplit=1" in plan(16, 8192, 57344, kernel_id=kernels.KERNEL_SKINNY | (8 << 4)) and plan(16, 8192, 1792, kernel_id=kernels.KERNEL_SKINNY | (7 << 4)).startswith("skinny ntw=7")
     assert plan(16, 28672, 8192).startswith("skinny ntw=8") and "grid=64x1x4 ksplit=4" in plan(16, 28672, 8192)

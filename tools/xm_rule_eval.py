@@ -26,7 +26,7 @@ def one_round(pairs, mt):
 
 
 def rule(M, K, N):
-    """-> (mb, pr) or None: the rule of make_plan (w4a16_gemm.hip), restated"""
+    """-> (mb, pr) or None: the rule of plan_xm (w4a16_plan.hip), restated"""
     pairs, KT = N // 32, K // 128
     if KT < 32 or M <= 16 or M > 128:
         return None

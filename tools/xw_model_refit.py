@@ -1,4 +1,4 @@
-"""Offline: the four-wave kernels' launch-time models (make_plan, `xwc`) against the three-box planner audit of the final r06 tree, a relative least-squares refit of their
+"""Offline: the four-wave kernels' launch-time models (pick_family in w4a16_plan.hip, `xwc`) against the three-box planner audit of the final r06 tree, a relative least-squares refit of their
 coefficients on the per-shape median, and which forced four-wave launch each set of coefficients would pick.
     python tools/xw_model_refit.py profiles/r06_planner_audit_raw/planner_audit_{c,d,e}.jsonl.gz
 Result (profiles/r06_xw_model_refit.txt): the shipped coefficients read 1.04-1.05 x the measured time (rms 5-8 %); refitted 2.6-4.9 %.  Among the forced four-wave variants the

@@ -246,6 +246,12 @@ int quick_decode_attention_f16(const void* q, const void* k_cache, const void* v
 int quick_decode_rope_attention_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos,
                                     void* k_cache, void* v_cache, void* out, int batch, int n_heads, int n_kv_heads,
                                     int head_dim, int cache_len, float scale, void* hip_stream);
+/* Which kernel quick_decode_rope_attention_f16 launches for this shape, as one line of text (host-only, no GPU needed): the kernel
+ * ("flash", "gqa" = the vector-ALU grouped-query sweep, "gqa-mfma"), query heads per workgroup, workgroups per KV head, waves per
+ * workgroup, cache rows per register set and the grid, e.g. "gqa-mfma heads=8 gsplit=1 waves=4 set_rows=64 grid=8x32".  The same
+ * refusals as the launch.  For logs and for tests of the dispatch; the wording may grow fields, the leading kernel word will not change. */
+int quick_decode_rope_attention_describe(int batch, int n_heads, int n_kv_heads, int head_dim, int cache_len, char* text,
+                                         size_t text_bytes);
 int quick_silu_mul_f16(const void* gate_up, void* y, int rows, int intermediate, void* hip_stream);
 
 /* lm_head of a decode step with the greedy arg-max folded in (the reference: torch linear + max on the fp16 layer AWQ leaves

@@ -3,6 +3,7 @@
 // extensions (awq_ext.layernorm_forward_cuda, quick/awq/modules/fused/norm.py:18; awq_ft_ext.single_query_attention,
 // quick/awq/modules/fused/attn.py:217) or from eager torch (attn.py:166-210); here they are small HBM/latency-bound
 // HIP kernels so that one decode layer is 9 launches instead of ~40.  fp16 in/out, fp32 arithmetic.
+#include <cstdio>
 #include <cstdlib>
 #include "w4a16_common.hpp"
 #include "../../include/quick_amd.h"
@@ -82,6 +83,7 @@ __global__ __launch_bounds__(64) void rope_kv_kernel(const half_t* __restrict__ 
   const int i = threadIdx.x;
   if (i >= D / 2) return;
   if (slot < nh + nkv) {
+    #pragma clang fp contract(off)  // (each product rounded to fp16 on its own: hipcc would fuse one into a v_fma_f16 with the add)
     const float x0 = (float)src[i], x1 = (float)src[i + D / 2];
     const float c0 = (float)cos_t[p * D + i], s0 = (float)sin_t[p * D + i];
     const float c1 = (float)cos_t[p * D + i + D / 2], s1 = (float)sin_t[p * D + i + D / 2];
@@ -111,6 +113,7 @@ __global__ __launch_bounds__(64) void rope_kv_prefill_kernel(const half_t* __res
   const int i = threadIdx.x;
   if (i >= D / 2) return;
   if (slot < nh + nkv) {
+    #pragma clang fp contract(off)  // (each product rounded to fp16 on its own: hipcc would fuse one into a v_fma_f16 with the add)
     const float x0 = (float)src[i], x1 = (float)src[i + D / 2];
     const float c0 = (float)cos_t[p * D + i], s0 = (float)sin_t[p * D + i];
     const float c1 = (float)cos_t[p * D + i + D / 2], s1 = (float)sin_t[p * D + i + D / 2];
@@ -229,6 +232,7 @@ __global__ __launch_bounds__(256) void decode_attention_kernel(const half_t* __r
 // problem between the workgroups of a group.
 __device__ __forceinline__ void rope8(const half8_t x, const half_t* __restrict__ cos_row, const half_t* __restrict__ sin_row,
                                       int sub, float (&r)[8]) {
+  #pragma clang fp contract(off)  // (each product rounded to fp16 on its own: hipcc would fuse one into a v_fma_f16 with the add)
   const half8_t c = *(const half8_t*)(cos_row + sub * 8), sn = *(const half8_t*)(sin_row + sub * 8);
   const float sign = sub < 8 ? -1.f : 1.f;  // rotate_half: dims 0..63 pair with -x[i+64], dims 64..127 with +x[i-64]
 #pragma unroll
@@ -318,6 +322,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_rope_attention_flash_kernel
   request(kva, vva, tb, L - 1);
   __builtin_amdgcn_sched_barrier(0);  // (hipcc otherwise hoists the wait for *pos and the cos / sin rows in front of these requests)
   {  // rotate q and the new k while the cache rows are in flight
+    #pragma clang fp contract(off)  // (each product rounded to fp16 on its own: hipcc would fuse one into a v_fma_f16 with the add)
     const half8_t cs = *(const half8_t*)(cos_t + (size_t)p * D + sub * 8), sn = *(const half8_t*)(sin_t + (size_t)p * D + sub * 8);
     const float sign = sub < 8 ? -1.f : 1.f;  // rotate_half: dims 0..63 pair with -x[i+64], dims 64..127 with +x[i-64]
 #pragma unroll
@@ -500,6 +505,7 @@ __global__ __launch_bounds__(256, 2) void decode_rope_attention_gqa_kernel(
   int tb = uniform(wave * 4);
   request(kva, vva, tb);
   {  // rotate the q heads and the new k while the first cache rows are in flight
+    #pragma clang fp contract(off)  // (each product rounded to fp16 on its own: hipcc would fuse one into a v_fma_f16 with the add)
     const half8_t cs = *(const half8_t*)(cos_t + (size_t)p * D + sub * 8), sn = *(const half8_t*)(sin_t + (size_t)p * D + sub * 8);
     const float sign = sub < 8 ? -1.f : 1.f;  // rotate_half: dims 0..63 pair with -x[i+64], dims 64..127 with +x[i-64]
 #pragma unroll
@@ -651,6 +657,7 @@ __global__ __launch_bounds__(256, 2) void decode_rope_attention_gqa_mfma_kernel(
   // rotate the q heads and the new k (dims 32 s + 8 rsel + j pair with the same j of k step s ^ 2) while the first rows are in flight
   half8_t qb[4], kh[4];
   {
+    #pragma clang fp contract(off)  // (each product rounded to fp16 on its own: hipcc would fuse one into a v_fma_f16 with the add)
     half8_t cs[4], sn[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -815,7 +822,9 @@ __global__ __launch_bounds__(256) void silu_mul_kernel(const half_t* __restrict_
 // (order-preserving bits of the fp16 logit, then the complement of the index: the maximum is the largest logit at the lowest
 // index) per wave -> per workgroup -> a second one-workgroup launch.  B <= 4 sequences (B * 16 accumulators).
 __device__ __forceinline__ unsigned long long argmax_key(half_t logit, unsigned idx) {
-  const unsigned bits = __builtin_bit_cast(unsigned, (float)logit);
+  // (-0 is folded into +0 first: the two compare equal, so the lower index must win between them as between any tied pair)
+  const float f = (float)logit;
+  const unsigned bits = f == 0.f ? 0u : __builtin_bit_cast(unsigned, f);
   const unsigned k = bits ^ ((bits >> 31) ? 0xffffffffu : 0x80000000u);
   return ((unsigned long long)k << 32) | (0xffffffffu - idx);
 }
@@ -972,6 +981,52 @@ __global__ void __launch_bounds__(256) prefetch_kernel(const unsigned* __restric
   if (acc == 0x9e3779b9u && sink) *sink = acc;  // (keeps the loads alive; sink is null)
 }
 
+// The kernel quick_decode_rope_attention_f16 launches for a shape: the one decision, shared with quick_decode_rope_attention_describe.
+struct AttentionPick {
+  enum Kind { FLASH, GQA, GQA_MFMA } kind;
+  int heads;    // query heads per workgroup
+  int gsplit;   // workgroups per KV head (grouped-query kernels; 1 for flash)
+  int waves;    // waves per workgroup
+};
+
+static int attention_check(int batch, int n_heads, int n_kv_heads, int head_dim, int cache_len) {
+  if (batch <= 0 || n_heads <= 0 || n_kv_heads <= 0 || head_dim != 128 || n_heads % n_kv_heads != 0) return QUICK_ERR_UNSUPPORTED;
+  if (batch > 65535 || cache_len <= 0) return QUICK_ERR_UNSUPPORTED;  // grid.y; the caller keeps *pos < cache_len (device value)
+  return QUICK_OK;
+}
+
+static AttentionPick attention_pick(int batch, int n_heads, int n_kv_heads, int cache_len) {
+  // grouped-query models with enough (sequence, KV head) pairs to fill the chip: one sweep over the cache per KV head
+  // (measured [r01]: 32 query / 8 KV heads, bs=64, 190 positions: 21.5 us against 32.6 us with a workgroup per query head;
+  // with fewer than ~256 workgroups the per-head kernels are ahead).  8 heads per KV head run as two workgroups of 4.
+  // (vector-ALU sweeps: four rows per slot and register set: 244 registers with four heads, two waves per SIMD; eight rows spill)
+  static const int mfma_on = [] {   // (A/B: QUICK_AMD_ATTN_MFMA=0 runs the vector-ALU sweeps)
+    const char* e = getenv("QUICK_AMD_ATTN_MFMA");
+    return e ? atoi(e) : 1;
+  }();
+  const int group = n_heads / n_kv_heads, pairs = batch * n_kv_heads;
+  // (8 heads per KV head from 128 pairs -- Llama-2-70B at bs = 16, one workgroup per pair on half the CUs -- measured 1 % BEHIND the two
+  // vector-ALU sweeps of 4 heads, profiles/r05_decode70_ab.txt)
+  if (mfma_on && group == 8 && pairs >= 256) return {AttentionPick::GQA_MFMA, 8, 1, 4};
+  if (mfma_on && group == 8 && pairs * 2 >= 256) return {AttentionPick::GQA_MFMA, 4, 2, 4};   // (fewer sequences: two workgroups of 4 heads per KV
+                                                                                               // head -- Llama-2-70B at bs = 16: 12.6 -> 11.4 us against
+                                                                                               // the vector-ALU sweeps, 1617 -> 1658 tok/s)
+  if (mfma_on && group == 4 && pairs >= 256) return {AttentionPick::GQA_MFMA, 4, 1, 4};   // (two chunks per set: 256 registers and a spill, 5-10 % behind)
+  if (group == 8 && pairs * 2 >= 256) return {AttentionPick::GQA, 4, 2, 4};
+  if (group == 4 && pairs >= 256) return {AttentionPick::GQA, 4, 1, 4};
+  if (group == 4 && pairs * 2 >= 256) return {AttentionPick::GQA, 2, 2, 4};   // fewer sequences: two workgroups of 2 heads per KV head
+  if (group == 2 && pairs >= 256) return {AttentionPick::GQA, 2, 1, 4};
+  // few workgroups and a cache longer than one four-wave trip: eight waves, 256 positions per trip; else four waves, 128 per trip
+  // [r05, profiles/r05_attention.txt: bs = 1, 192 / 512 positions 5.39 / 8.6 -> 5.15 / 7.5 us, 128 positions 4.24 against 5.0; from 256
+  // workgroups on the four-wave form is ahead everywhere; sixteen waves x 4 rows and four waves x 16 rows measured behind both]
+  static const int forced = [] {   // (A/B runs: 4 or 8 waves)
+    const char* e = getenv("QUICK_AMD_ATTN_WAVES");
+    return e ? atoi(e) : 0;
+  }();
+  const int pick = forced ? forced : (((long)n_heads * batch <= 128 && cache_len > 128) ? 8 : 4);
+  return {AttentionPick::FLASH, 1, 1, pick == 8 ? 8 : 4};
+}
+
 }  // namespace quick_amd
 
 using namespace quick_amd;
@@ -994,7 +1049,8 @@ int quick_rmsnorm_f16(const void* x, const void* weight, void* y, int rows, int 
 int quick_rope_kv_append_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos, void* q_out,
                              void* k_cache, void* v_cache, int batch, int n_heads, int n_kv_heads, int head_dim,
                              int cache_len, void* hip_stream) {
-  if (batch <= 0 || head_dim % 2 != 0 || head_dim > 128 || n_heads % n_kv_heads != 0) return QUICK_ERR_INVALID_ARGUMENT;
+  if (batch <= 0 || n_heads <= 0 || n_kv_heads <= 0 || head_dim % 2 != 0 || head_dim > 128 || n_heads % n_kv_heads != 0)
+    return QUICK_ERR_INVALID_ARGUMENT;
   if (batch > 65535) return QUICK_ERR_UNSUPPORTED;  // grid.y
   hipLaunchKernelGGL(rope_kv_kernel, dim3(n_heads + 2 * n_kv_heads, batch), dim3(64), 0, (hipStream_t)hip_stream,
                      (const half_t*)qkv, (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos,
@@ -1005,7 +1061,8 @@ int quick_rope_kv_append_f16(const void* qkv, const void* cos_table, const void*
 int quick_rope_kv_write_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos0, void* q_out,
                             void* k_cache, void* v_cache, int batch, int tokens, int n_heads, int n_kv_heads, int head_dim,
                             int cache_len, void* hip_stream) {
-  if (batch <= 0 || tokens <= 0 || head_dim % 2 != 0 || head_dim > 128 || n_heads % n_kv_heads != 0) return QUICK_ERR_INVALID_ARGUMENT;
+  if (batch <= 0 || tokens <= 0 || n_heads <= 0 || n_kv_heads <= 0 || head_dim % 2 != 0 || head_dim > 128 || n_heads % n_kv_heads != 0)
+    return QUICK_ERR_INVALID_ARGUMENT;
   if ((long)batch * tokens > 65535) return QUICK_ERR_UNSUPPORTED;  // grid.y
   hipLaunchKernelGGL(rope_kv_prefill_kernel, dim3(n_heads + 2 * n_kv_heads, batch * tokens), dim3(64), 0, (hipStream_t)hip_stream,
                      (const half_t*)qkv, (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos0, (half_t*)q_out,
@@ -1016,7 +1073,8 @@ int quick_rope_kv_write_f16(const void* qkv, const void* cos_table, const void* 
 int quick_decode_attention_f16(const void* q, const void* k_cache, const void* v_cache, const void* pos, void* out,
                                int batch, int n_heads, int n_kv_heads, int head_dim, int cache_len, float scale,
                                void* hip_stream) {
-  if (batch <= 0 || batch > 65535 || head_dim != 128 || n_heads % n_kv_heads != 0) return QUICK_ERR_UNSUPPORTED;
+  if (batch <= 0 || batch > 65535 || n_heads <= 0 || n_kv_heads <= 0 || head_dim != 128 || n_heads % n_kv_heads != 0)
+    return QUICK_ERR_UNSUPPORTED;
   const size_t lds = (((size_t)cache_len + 3) & ~(size_t)3) * 4 + 4 * 128 * 4;
   if (lds > 64 * 1024) return QUICK_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(decode_attention_kernel, dim3(n_heads, batch), dim3(256), (unsigned)lds, (hipStream_t)hip_stream,
@@ -1028,62 +1086,55 @@ int quick_decode_attention_f16(const void* q, const void* k_cache, const void* v
 int quick_decode_rope_attention_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos,
                                     void* k_cache, void* v_cache, void* out, int batch, int n_heads, int n_kv_heads,
                                     int head_dim, int cache_len, float scale, void* hip_stream) {
-  if (batch <= 0 || head_dim != 128 || n_heads % n_kv_heads != 0) return QUICK_ERR_UNSUPPORTED;
-  if (batch > 65535 || cache_len <= 0) return QUICK_ERR_UNSUPPORTED;  // grid.y; the caller keeps *pos < cache_len (device value)
-#define QA_GQA(GROUP, UNR, GSPLIT)                                                                                 \
-  hipLaunchKernelGGL((decode_rope_attention_gqa_kernel<GROUP, UNR>), dim3(n_kv_heads * (GSPLIT), batch), dim3(256), 0, \
-                     (hipStream_t)hip_stream, (const half_t*)qkv, (const half_t*)cos_table, (const half_t*)sin_table, \
-                     (const long*)pos, (half_t*)k_cache, (half_t*)v_cache, (half_t*)out, n_heads, n_kv_heads,       \
-                     cache_len, scale, GSPLIT)
-  // grouped-query models with enough (sequence, KV head) pairs to fill the chip: one sweep over the cache per KV head
-  // (measured [r01]: 32 query / 8 KV heads, bs=64, 190 positions: 21.5 us against 32.6 us with a workgroup per query head;
-  // with fewer than ~256 workgroups the per-head kernels are ahead).  8 heads per KV head run as two workgroups of 4.
-  const int group = n_heads / n_kv_heads;
-  if (group == 2 || group == 4 || group == 8) {
-    const int pairs = batch * n_kv_heads;
-    bool done = true;
-    // (four rows per slot and register set: 244 registers with four heads, two waves per SIMD; eight rows spill)
-#define QA_GQA_U(GROUP, GSPLIT) QA_GQA(GROUP, 4, GSPLIT)
-    static const int mfma_on = [] {   // (A/B: QUICK_AMD_ATTN_MFMA=0 runs the vector-ALU sweeps)
-      const char* e = getenv("QUICK_AMD_ATTN_MFMA");
-      return e ? atoi(e) : 1;
-    }();
-#define QA_GQA_M(GROUP, UC, GSPLIT)                                                                                  \
-  hipLaunchKernelGGL((decode_rope_attention_gqa_mfma_kernel<GROUP, UC>), dim3(n_kv_heads * (GSPLIT), batch), dim3(256), 0, \
-                     (hipStream_t)hip_stream, (const half_t*)qkv, (const half_t*)cos_table, (const half_t*)sin_table, \
-                     (const long*)pos, (half_t*)k_cache, (half_t*)v_cache, (half_t*)out, n_heads, n_kv_heads, cache_len, scale, GSPLIT)
-    // (8 heads per KV head from 128 pairs -- Llama-2-70B at bs = 16, one workgroup per pair on half the CUs -- measured 1 % BEHIND the two
-    // vector-ALU sweeps of 4 heads, profiles/r05_decode70_ab.txt)
-    if (mfma_on && group == 8 && pairs >= 256) QA_GQA_M(8, 1, 1);
-    else if (mfma_on && group == 8 && pairs * 2 >= 256) QA_GQA_M(4, 1, 2);   // (fewer sequences: two workgroups of 4 heads per KV head -- Llama-2-70B at
-                                                                             // bs = 16: 12.6 -> 11.4 us against the vector-ALU sweeps, 1617 -> 1658 tok/s)
-    else if (mfma_on && group == 4 && pairs >= 256) QA_GQA_M(4, 1, 1);   // (two chunks per set: 256 registers and a spill, 5-10 % behind)
-    else if (group == 8 && pairs * 2 >= 256) QA_GQA_U(4, 2);
-    else if (group == 4 && pairs >= 256) QA_GQA_U(4, 1);
-    else if (group == 4 && pairs * 2 >= 256) QA_GQA_U(2, 2);  // fewer sequences: two workgroups of 2 heads per KV head
-    else if (group == 2 && pairs >= 256) QA_GQA_U(2, 1);
-    else done = false;
-#undef QA_GQA_U
-#undef QA_GQA_M
-    if (done) return hipGetLastError() == hipSuccess ? QUICK_OK : QUICK_ERR_LAUNCH;
+  const int rc = attention_check(batch, n_heads, n_kv_heads, head_dim, cache_len);
+  if (rc != QUICK_OK) return rc;
+  const AttentionPick a = attention_pick(batch, n_heads, n_kv_heads, cache_len);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const dim3 grid_gqa(n_kv_heads * a.gsplit, batch);
+#define QA_GQA(GROUP)                                                                                                          \
+  hipLaunchKernelGGL((decode_rope_attention_gqa_kernel<GROUP, 4>), grid_gqa, dim3(256), 0, st, (const half_t*)qkv,            \
+                     (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos, (half_t*)k_cache, (half_t*)v_cache, \
+                     (half_t*)out, n_heads, n_kv_heads, cache_len, scale, a.gsplit)
+#define QA_GQA_M(GROUP)                                                                                                        \
+  hipLaunchKernelGGL((decode_rope_attention_gqa_mfma_kernel<GROUP, 1>), grid_gqa, dim3(256), 0, st, (const half_t*)qkv,       \
+                     (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos, (half_t*)k_cache, (half_t*)v_cache, \
+                     (half_t*)out, n_heads, n_kv_heads, cache_len, scale, a.gsplit)
+#define QA_FLASH(W)                                                                                                            \
+  hipLaunchKernelGGL((decode_rope_attention_flash_kernel<W, 4>), dim3(n_heads, batch), dim3((W) * 64), 0, st,                 \
+                     (const half_t*)qkv, (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos,                 \
+                     (half_t*)k_cache, (half_t*)v_cache, (half_t*)out, n_heads, n_kv_heads, cache_len, scale)
+  switch (a.kind) {
+    case AttentionPick::GQA_MFMA:
+      if (a.heads == 8) QA_GQA_M(8);
+      else QA_GQA_M(4);
+      break;
+    case AttentionPick::GQA:
+      if (a.heads == 4) QA_GQA(4);
+      else QA_GQA(2);
+      break;
+    case AttentionPick::FLASH:
+      if (a.waves == 8) QA_FLASH(8);   // (two register sets of 4 rows per slot: the same 256 / 128 positions in flight as one set of 8)
+      else QA_FLASH(4);
+      break;
   }
 #undef QA_GQA
-  // few workgroups and a cache longer than one four-wave trip: eight waves, 256 positions per trip; else four waves, 128 per trip
-  // [r05, profiles/r05_attention.txt: bs = 1, 192 / 512 positions 5.39 / 8.6 -> 5.15 / 7.5 us, 128 positions 4.24 against 5.0; from 256
-  // workgroups on the four-wave form is ahead everywhere; sixteen waves x 4 rows and four waves x 16 rows measured behind both]
-#define QA_FLASH(W, U)                                                                                                       \
-  hipLaunchKernelGGL((decode_rope_attention_flash_kernel<W, U>), dim3(n_heads, batch), dim3((W) * 64), 0, (hipStream_t)hip_stream, \
-                     (const half_t*)qkv, (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos,               \
-                     (half_t*)k_cache, (half_t*)v_cache, (half_t*)out, n_heads, n_kv_heads, cache_len, scale)
-  static const int forced = [] {   // (A/B runs: 4 or 8 waves)
-    const char* e = getenv("QUICK_AMD_ATTN_WAVES");
-    return e ? atoi(e) : 0;
-  }();
-  const int pick = forced ? forced : (((long)n_heads * batch <= 128 && cache_len > 128) ? 8 : 4);
-  if (pick == 8) QA_FLASH(8, 4);   // (two register sets of 4 rows per slot: the same 256 / 128 positions in flight as one set of 8)
-  else QA_FLASH(4, 4);
+#undef QA_GQA_M
 #undef QA_FLASH
   return hipGetLastError() == hipSuccess ? QUICK_OK : QUICK_ERR_LAUNCH;
+}
+
+int quick_decode_rope_attention_describe(int batch, int n_heads, int n_kv_heads, int head_dim, int cache_len, char* text,
+                                         size_t text_bytes) {
+  const int rc = attention_check(batch, n_heads, n_kv_heads, head_dim, cache_len);
+  if (rc != QUICK_OK) return rc;
+  if (!text || text_bytes == 0) return QUICK_ERR_INVALID_ARGUMENT;
+  const AttentionPick a = attention_pick(batch, n_heads, n_kv_heads, cache_len);
+  static const char* const names[] = {"flash", "gqa", "gqa-mfma"};
+  const int rows = a.kind == AttentionPick::FLASH ? a.waves * 4 * 4 : 64;   // cache rows one register set of the workgroup holds
+  const unsigned gx = a.kind == AttentionPick::FLASH ? (unsigned)n_heads : (unsigned)(n_kv_heads * a.gsplit);
+  snprintf(text, text_bytes, "%s heads=%d gsplit=%d waves=%d set_rows=%d grid=%ux%d", names[a.kind], a.heads, a.gsplit, a.waves, rows,
+           gx, batch);
+  return QUICK_OK;
 }
 
 int quick_silu_mul_f16(const void* gate_up, void* y, int rows, int intermediate, void* hip_stream) {
@@ -1101,9 +1152,9 @@ int quick_lm_head_argmax_f16(const void* x, const void* norm_weight, float eps, 
                              void* hip_stream) {
   if (!x || !weight || !next_token || !workspace) return QUICK_ERR_INVALID_ARGUMENT;
   if (batch < 1 || batch > 4 || vocab < 1 || hidden < 512 || hidden % 512 != 0) return QUICK_ERR_UNSUPPORTED;
-  if (workspace_bytes < quick_lm_head_workspace_bytes(batch)) return QUICK_ERR_WORKSPACE;
   const size_t lds = (size_t)batch * hidden * 2;
   if (lds > 72 * 1024) return QUICK_ERR_UNSUPPORTED;  // two workgroups per CU
+  if (workspace_bytes < quick_lm_head_workspace_bytes(batch)) return QUICK_ERR_WORKSPACE;
   const int nblk = (vocab + 3) / 4;
   const unsigned grid = (unsigned)std::min(512, (nblk + 7) / 8);
   hipStream_t st = (hipStream_t)hip_stream;

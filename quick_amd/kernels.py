@@ -383,6 +383,15 @@ def rope_attention(qkv, cos_table, sin_table, pos, k_cache, v_cache, out, n_head
     return out
 
 
+def attention_describe(batch, n_heads, n_kv_heads, head_dim, cache_len):
+    """One line saying which kernel rope_attention runs for this shape (quick_decode_rope_attention_describe; host-only, no GPU needed)."""
+    buf = ctypes.create_string_buffer(128)
+    rc = _lib.load().quick_decode_rope_attention_describe(batch, n_heads, n_kv_heads, head_dim, cache_len, buf, len(buf))
+    if rc != _OK:
+        _raise(rc)
+    return buf.value.decode()
+
+
 _LM_WS = {}
 
 

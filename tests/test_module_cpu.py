@@ -1,5 +1,6 @@
 """WQLinear_QUICK host logic and the C-ABI surface, no GPU needed."""
 import ctypes
+import json
 import os
 import sys
 import re
@@ -732,3 +733,106 @@ def test_generated_mid_token_loops_are_what_the_generator_writes(tmp_path, monke
             waits = [i.text for i in copy if i.text.startswith("s_waitcnt vmcnt")]
             assert len(waits) == 5 and all(int(w.split("(")[1].rstrip(")")) <= 63 for w in waits)
         assert 16 * c.MB * c.PR <= c.AXF and c.VEND <= 128      # accumulators below the x fragments; the 512-thread workgroup's 128 VGPRs
+
+
+def _attention_table(B, nh, nkv, L):
+    """The dispatch of quick_decode_rope_attention_f16 with the A/B switches unset, restated: (kernel word, heads per workgroup, gsplit, waves)."""
+    group, pairs = nh // nkv, B * nkv
+    if group == 8 and pairs >= 256:
+        return "gqa-mfma", 8, 1, 4
+    if group == 8 and pairs >= 128:
+        return "gqa-mfma", 4, 2, 4
+    if group == 4 and pairs >= 256:
+        return "gqa-mfma", 4, 1, 4
+    if group == 4 and pairs >= 128:
+        return "gqa", 2, 2, 4
+    if group == 2 and pairs >= 256:
+        return "gqa", 2, 1, 4
+    return "flash", 1, 1, (8 if B * nh <= 128 and L > 128 else 4)
+
+
+def test_attention_describe_pins_the_dispatch():
+    """quick_decode_rope_attention_describe is host-only and makes the launcher's own decision.  Pinned: the decoder configs at the batch
+    sizes the benchmarks run, the pair boundaries 127 / 128 / 255 / 256, the flash wave boundary at cache_len 128 / 129, and the groups
+    that no grouped-query kernel serves (1, 3, 16)."""
+    import subprocess
+    code = r"""
+import json, sys
+from quick_amd import kernels
+print(json.dumps([kernels.attention_describe(B, nh, nkv, 128, L) for B, nh, nkv, L in json.loads(sys.argv[1])]))
+"""
+    from quick_amd.decoder import CONFIGS
+    cases = []
+    for name in ("llama2-7b", "mistral-7b", "llama2-70b", "tiny"):
+        c = CONFIGS[name]
+        for B in (1, 4, 16, 32, 64):
+            for L in (128, 129, 4096):
+                cases.append((B, c.heads, c.kv_heads, L))
+    for group in (2, 4, 8):                     # pairs = B * nkv at 127 / 128 / 255 / 256
+        for B, nkv in ((127, 1), (128, 1), (255, 1), (256, 1), (16, 8), (32, 8), (15, 17), (17, 15), (51, 5), (64, 4)):
+            cases.append((B, group * nkv, nkv, 4096))
+    for group in (1, 3, 16):                    # flash whatever the pairs
+        for B, nkv in ((1, 8), (16, 8), (32, 8), (64, 8), (256, 1), (4, 2)):
+            for L in (128, 129):
+                cases.append((B, group * nkv, nkv, L))
+    cases += [(1, 128, 8, 129), (1, 129, 1, 129), (2, 64, 64, 129), (2, 64, 64, 128), (3, 43, 43, 129), (65535, 1, 1, 4096)]
+    env = {k: v for k, v in os.environ.items() if k not in ("QUICK_AMD_ATTN_MFMA", "QUICK_AMD_ATTN_WAVES")}
+    r = subprocess.run([sys.executable, "-c", code, json.dumps(cases)], capture_output=True, text=True, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stderr
+    texts = json.loads(r.stdout.strip().splitlines()[-1])
+    seen = set()
+    for (B, nh, nkv, L), text in zip(cases, texts):
+        word, heads, gsplit, waves = _attention_table(B, nh, nkv, L)
+        want = f"{word} heads={heads} gsplit={gsplit} waves={waves} set_rows={waves * 16 if word == 'flash' else 64} "
+        grid = f"grid={nh if word == 'flash' else nkv * gsplit}x{B}"
+        assert text.startswith(want) and text.endswith(grid), (B, nh, nkv, L, text, want, grid)
+        seen.add(want)
+    assert len(seen) == 7, seen                 # every branch of the table was reached (flash with 4 and with 8 waves)
+    # the decoder shapes the issue's table names
+    from quick_amd import kernels
+    assert kernels.attention_describe(16, 64, 8, 128, 4096).startswith("gqa-mfma heads=4 gsplit=2")     # Llama-2-70B bs 16
+    assert kernels.attention_describe(32, 32, 8, 128, 4096).startswith("gqa-mfma heads=4 gsplit=1")     # Mistral-7B bs 32
+    assert kernels.attention_describe(1, 32, 32, 128, 4096).startswith("flash heads=1 gsplit=1 waves=8")   # Llama-2-7B bs 1
+    assert kernels.attention_describe(64, 32, 32, 128, 4096).startswith("flash heads=1 gsplit=1 waves=4")  # Llama-2-7B bs 64
+
+
+def test_decode_entry_points_refuse_before_launching():
+    """The decode-step C entry points validate their arguments before they launch anything: these calls pass null device pointers (the
+    lm_head ones a zero-byte workspace, refused last) and must come back with the documented error code."""
+    lib = _lib.load()
+    INVALID, WORKSPACE, UNSUPPORTED = 1, 2, 4
+    buf = ctypes.create_string_buffer(128)
+    # RMSNorm: hidden % 8 != 0
+    for H in (4, 12, 4100, 0, -8):
+        assert lib.quick_rmsnorm_f16(None, None, None, 2, H, 1e-5, None) == INVALID, H
+    assert lib.quick_rmsnorm_f16(None, None, None, 0, 512, 1e-5, None) == INVALID
+    # RoPE + KV append / prefill write: odd or too large head_dim, head counts, grid.y
+    for D in (127, 63, 130, 256):
+        assert lib.quick_rope_kv_append_f16(None, None, None, None, None, None, None, 1, 8, 2, D, 64, None) == INVALID, D
+        assert lib.quick_rope_kv_write_f16(None, None, None, None, None, None, None, 1, 4, 8, 2, D, 64, None) == INVALID, D
+    for nh, nkv in ((8, 3), (8, 0), (0, 2), (-8, 2)):
+        assert lib.quick_rope_kv_append_f16(None, None, None, None, None, None, None, 1, nh, nkv, 128, 64, None) == INVALID, (nh, nkv)
+        assert lib.quick_rope_kv_write_f16(None, None, None, None, None, None, None, 1, 4, nh, nkv, 128, 64, None) == INVALID, (nh, nkv)
+    assert lib.quick_rope_kv_append_f16(None, None, None, None, None, None, None, 65536, 8, 2, 128, 64, None) == UNSUPPORTED
+    assert lib.quick_rope_kv_write_f16(None, None, None, None, None, None, None, 65536, 1, 8, 2, 128, 64, None) == UNSUPPORTED
+    assert lib.quick_rope_kv_write_f16(None, None, None, None, None, None, None, 256, 257, 8, 2, 128, 64, None) == UNSUPPORTED   # B * T = 65792
+    assert lib.quick_rope_kv_write_f16(None, None, None, None, None, None, None, 1, 65536, 8, 2, 128, 64, None) == UNSUPPORTED
+    # fused RoPE + attention (and its describe): head_dim 128 only, batch <= 65535, whole groups
+    for args in ((1, 8, 2, 64, 64), (1, 8, 2, 127, 64), (65536, 8, 2, 128, 64), (1, 8, 3, 128, 64), (1, 8, 0, 128, 64), (0, 8, 2, 128, 64),
+                 (1, 8, 2, 128, 0)):
+        assert lib.quick_decode_rope_attention_f16(None, None, None, None, None, None, None, *args, 0.1, None) == UNSUPPORTED, args
+        assert lib.quick_decode_rope_attention_describe(*args, buf, len(buf)) == UNSUPPORTED, args
+    assert lib.quick_decode_rope_attention_describe(1, 8, 2, 128, 64, None, 0) == INVALID
+    # the two-pass kernel: scores of the whole cache in LDS, cache_len <= 15872
+    assert lib.quick_decode_attention_f16(None, None, None, None, None, 1, 8, 2, 128, 15873, 0.1, None) == UNSUPPORTED
+    for args in ((1, 8, 2, 64, 64), (65536, 8, 2, 128, 64), (1, 8, 3, 128, 64), (1, 8, 0, 128, 64)):
+        assert lib.quick_decode_attention_f16(None, None, None, None, None, *args, 0.1, None) == UNSUPPORTED, args
+    # lm_head: batch <= 4, hidden % 512 == 0, batch * hidden <= 36864 -- refused ahead of the (zero-byte) workspace
+    fake = ctypes.c_void_p(1 << 40)
+    lm = lambda B, V, H, ws=0: lib.quick_lm_head_argmax_f16(fake, None, 1e-5, fake, None, None, fake, fake, ws, B, V, H, None)
+    assert lib.quick_lm_head_argmax_f16(None, None, 1e-5, None, None, None, None, None, 0, 1, 1000, 4096, None) == INVALID
+    for B, V, H in ((5, 1000, 512), (0, 1000, 512), (1, 1000, 4000), (2, 1000, 256), (1, 1000, 0), (4, 1000, 9728), (1, 1000, 37376),
+                    (2, 1000, 18944), (3, 1000, 12800), (1, 0, 512)):
+        assert lm(B, V, H) == UNSUPPORTED, (B, V, H)
+    for B, H in ((4, 9216), (1, 36864), (2, 18432)):   # at the LDS limit: only the workspace is missing
+        assert lm(B, 1000, H) == WORKSPACE, (B, H)

@@ -143,6 +143,9 @@ int quick_w4a16_workspace_check(const void* workspace, size_t workspace_bytes, v
  *   bit 25      SKINNY: exact per-weight dequantisation (no deferred zero point)
  *   bits 26-28  SKINNY: 26 force the table deferred-zero path, 28 no fragment deferred-zero path; TILED: 27 force 128 x 256
  *               four-wave tiles; XK: weight queue depth in stages (3..6)
+ *               XW (bits 27-28): staggered K ranges of the two-slice 128 x 128 launch, d = 1..3 stages of 128 k -- each slice finishes the
+ *               blocks it does not own 2 d stages early and mails them while it multiplies on for its own; needs G = 128,
+ *               an even K / 128 and K / 256 - d >= 4, anything else is planned without it (plan_describe says `stagger=<d>` when taken)
  *   bits 29-30  TILED: force / forbid 256-channel tiles
  * Environment: QUICK_AMD_EXCHANGE_CUS=<n> -- a SPEED hint since r04: the K slices of an XK launch exchange fastest when tiles x slices
  * workgroups are co-resident, and the planner sizes the slice count for the device's CU count; a process whose queues see fewer CUs (a

@@ -1419,6 +1419,10 @@ static int run_gemm(const void* x, const void* qweight, const void* scales, cons
     else if (p.ablate) return fail(QUICK_ERR_INVALID_ARGUMENT, "XW: timing-experiment bits 16 (stamps) and 20 (no exchange) only");
 #endif
     a.xcd_gm |= p.poll_log2 << 8;  // (the kernel reads the tile-order rows from the low byte)
+    if (p.xw_stagger) {            // staggered K ranges: its own build, d in bits 16-17
+      abl |= 128;
+      a.xcd_gm |= p.xw_stagger << 16;
+    }
     if (!xw_launch(p.wide_mb, p.wide_pairs, p.ksplit, abl, a, p.ntiles * p.ksplit, L.st, L.start, L.stop)) {
       if (abl == 32) g_span_unsupported = true;
       return fail(QUICK_ERR_UNSUPPORTED, "no four-wave build for tokens=%d channels=%d slices=%d abl=%d", p.wide_mb * 32, p.tch, p.ksplit, abl);

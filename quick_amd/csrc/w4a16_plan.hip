@@ -533,6 +533,11 @@ static int within_limits(const Req& r, const Pick& k) {
 // bits 4-7: 32-token blocks per tile (2, 4; 0 = 4); bit 12: 128-channel tiles (implied by 2 blocks); bits 8-11: S (0 = as many as fit
 // the CUs); bits 22-26: log2 of the poll limit in ticks of 10 ns (tests: 1 = every wave gives up at once).
 // (bits 4-7 = 8: the 256 x 256 tile -- waves of 256 tokens x 64 channels, a ring of two 64 KiB slots, one slice only)
+// AUTO's rule for the staggered two-slice launch: stages (128 k) per slice and output tiles
+#ifndef QA_XW_STAGGER_AUTO_D
+#define QA_XW_STAGGER_AUTO_D 1   // (A/B builds: -DQA_XW_STAGGER_AUTO_D=2 / 3)
+#endif
+static bool xw_stagger_auto(int stages_per_slice, int tiles) { return tiles == 128 && stages_per_slice >= 16; }
 static void shape_xw(const Req& r, const Pick& k, Plan& p) {
   const int M = r.M, N = r.N, KT = r.KT;
   int mb, pairs;
@@ -554,6 +559,13 @@ static void shape_xw(const Req& r, const Pick& k, Plan& p) {
   p.kt_per_split = (KT + s - 1) / s;
   p.poll_log2 = r.id.poll_log2;
   if (const char* e = getenv("QUICK_AMD_EXCHANGE_POLL_LOG2")) p.poll_log2 = std::max(0, std::min(31, atoi(e)));
+  // Staggered K ranges (bits 27-28 = d): only the two-slice 128 x 128 launch with G = 128, an even number of k tiles and a phase 1 of at
+  // least the ring's four stages has the build; anything else is planned WITHOUT it.  AUTO (kernel id 0) takes d = 2 where it was measured
+  // ahead (profiles/r07_ab_stagger.txt): one workgroup per CU half of the chip or more, 16 stages per slice or more.
+  p.xw_stagger = 0;
+  const auto stagger_fits = [&](int d) { return mb == 4 && pairs == 1 && s == 2 && r.G == 128 && KT % 2 == 0 && KT / 2 - d >= 4; };
+  if (r.id.xw_stagger) p.xw_stagger = stagger_fits(r.id.xw_stagger) ? r.id.xw_stagger : 0;
+  else if (r.bare && xw_stagger_auto(KT / 2, p.ntiles) && stagger_fits(QA_XW_STAGGER_AUTO_D)) p.xw_stagger = QA_XW_STAGGER_AUTO_D;
   // XCDs per K slice: they form a gm x gn grid over the (token, channel) tiles; bytes per k and XCD: x rows (2 B) + weight columns (1/2 B)
   p.xcd_gm = xcd_rows(r, (long)p.ntiles * s, MBk, NBk, 8 / s, 64L * mb, 64L * pairs);
 }
@@ -936,8 +948,12 @@ void plan_describe(int M, int K, int N, int G, int kernel, int grid_split_k, cha
              p.xlds ? "lds" : "l2", p.dz ? (p.xlds ? "deferred-zero-table" : "deferred-zero-fragment") : "exact", p.grid_x,
              (M + 15) / 16, p.ksplit, p.ksplit, workspace_need(p));
   else if (p.kernel == QUICK_KERNEL_XW)
-    snprintf(text, text_bytes, "xw tokens=%d channels=%d waves=4 ring=%d queue=%d grid=%d slices=%d xcd_rows=%d workspace=%zu", p.wide_mb * 32, p.tch,
-             p.wide_mb == 2 ? 8 : (p.wide_mb == 8 ? 2 : 4), p.wide_mb == 2 ? 8 : (p.wide_mb == 8 ? 2 : 4), p.ntiles * p.ksplit, p.ksplit, p.xcd_gm, workspace_need(p));
+  {
+    char stg[16] = "";
+    if (p.xw_stagger) snprintf(stg, sizeof stg, " stagger=%d", p.xw_stagger);
+    snprintf(text, text_bytes, "xw tokens=%d channels=%d waves=4 ring=%d queue=%d grid=%d slices=%d xcd_rows=%d%s workspace=%zu", p.wide_mb * 32, p.tch,
+             p.wide_mb == 2 ? 8 : (p.wide_mb == 8 ? 2 : 4), p.wide_mb == 2 ? 8 : (p.wide_mb == 8 ? 2 : 4), p.ntiles * p.ksplit, p.ksplit, p.xcd_gm, stg, workspace_need(p));
+  }
   else if (p.kernel == QUICK_KERNEL_XK)
     snprintf(text, text_bytes, "xk tokens=%d channels=128 waves=%d ring=%d queue=%d grid=%d slices=%d xcd_rows=%d workspace=%zu", p.wide_mb * 32,
              p.xk_loader ? 12 : (p.xk_kq == 4 ? 16 : 8), p.xk_loader ? 3 : p.xk_nbuf, p.xk_loader ? 5 : p.xk_wd, p.ntiles * p.ksplit, p.ksplit, p.xcd_gm, workspace_need(p));

@@ -33,11 +33,12 @@ struct KernelId {
   bool force256;     // bit 29: TILED 256-channel tiles
   bool forbid256;    // bit 30: TILED no 256-channel tiles
   bool high;         // any bit from 12 up
+  int xw_stagger;    // bits 27-28: XW staggered K ranges of the two-slice 128 x 128 launch, d = 1..3 (0 = today's launch)
 };
 inline KernelId decode_kernel_id(int k) {
   return {k & 15, (k >> 4) & 15, (k >> 8) & 15, ((k >> 8) & 15) * 4, (k >> 8) & 3, ((k >> 12) & 1) != 0, ((k >> 13) & 1) != 0, ((k >> 14) & 1) != 0,
           ((k >> 15) & 1) != 0, (k >> 16) & 31, ((k >> 21) & 1) != 0, (k >> 22) & 7, (k >> 22) & 31, ((k >> 25) & 1) != 0, ((k >> 26) & 1) != 0,
-          (k >> 26) & 7, ((k >> 27) & 1) != 0, ((k >> 28) & 1) != 0, ((k >> 29) & 1) != 0, ((k >> 30) & 1) != 0, (k >> 12) != 0};
+          (k >> 26) & 7, ((k >> 27) & 1) != 0, ((k >> 28) & 1) != 0, ((k >> 29) & 1) != 0, ((k >> 30) & 1) != 0, (k >> 12) != 0, (k >> 27) & 3};
 }
 
 struct Plan {
@@ -60,6 +61,7 @@ struct Plan {
   int xk_nbuf, xk_wd;  // exchange-K: x ring slots, weight queue depth (wide_mb = token tiles of 32, ksplit = slices that exchange)
   bool xk_loader;      // exchange-K: the twelve-wave flavour (four loader waves; kernel bit 12)
   int xk_kq;           // exchange-K: K groups of waves per workgroup, 2 (eight waves) or 4 (sixteen; kernel bit 13)
+  int xw_stagger;      // XW, 128 x 128 tiles with two slices: stagger d of the slices' K ranges in 128-k stages (w4a16_xw.hpp), 0 = none
   int poll_log2;       // XW: log2 of the ticks (10 ns) a wave waits for a partner slice before it gives its block up (0 = the kernel's default)
   int lean_tmax;       // LEAN: the most k tiles a wave may own (the build's register ring), 0 = no build for this shape
   int frag8_t;         // SKINNY, mt == 8: k tiles per wave of the straight-line eight-tile fragment kernel (w4a16_frag8_kernel), 0 = not that kernel

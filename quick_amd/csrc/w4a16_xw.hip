@@ -47,6 +47,18 @@ static bool xw_go_t(int mb, int pairs, int s, const GemmArgs& a, int workgroups,
 
 bool xw_launch(int mb, int pairs, int slices, int abl, const GemmArgs& a, int workgroups, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
   if (a.G % 128 != 0 || (a.tpg & (a.tpg - 1)) != 0) return false;   // the loop shifts the k tile by log2(k tiles per group)
+  if (abl & 128) {   // staggered K ranges: 128 x 128 tiles, two slices, G = 128 (w4a16_xw.hpp; the planner asks for nothing else)
+    if (!(mb == 4 && pairs == 1 && slices == 2 && a.tpg == 1)) return false;
+    switch (abl) {
+      case 128: return xw_go<4, 1, 2, 128>(a, workgroups, st, start, stop);
+      case 160: return xw_go<4, 1, 2, 160>(a, workgroups, st, start, stop);
+#ifdef QUICK_AMD_TOOLS
+      case 192: return xw_go<4, 1, 2, 192>(a, workgroups, st, start, stop);
+      case 196: return xw_go<4, 1, 2, 196>(a, workgroups, st, start, stop);
+#endif
+      default: return false;
+    }
+  }
   switch (abl) {
     case 0: return xw_go_t<0>(mb, pairs, slices, a, workgroups, st, start, stop);
     case 32: return xw_go_t<32>(mb, pairs, slices, a, workgroups, st, start, stop);

@@ -25,7 +25,10 @@ gen = torch.Generator(device=dev).manual_seed(7)
 cases = []
 for (M, K, N), kid in (((512, 4096, 4096), xw(4, 2, 4)), ((512, 4096, 4096), xw(4, 1, 2)), ((256, 4096, 4096), xw(2, 1, 2)), ((1024, 4096, 4096), xw(4, 2, 2)),
                        ((128, 8192, 2048), xw(4, 1, 4)), ((300, 2048, 4096), xw(4, 1, 2)), ((128, 4096, 4096), xk(2, 4)), ((64, 11008, 4096), xk(2, 8)),
-                       ((512, 4096, 4096), xk(4, 2)), ((200, 4096, 2048), xk(4, 4)), ((64, 4096, 6144), xk(2, 4)), ((96, 8192, 1024), xk(2, 8))):
+                       ((512, 4096, 4096), xk(4, 2)), ((200, 4096, 2048), xk(4, 4)), ((64, 4096, 6144), xk(2, 4)), ((96, 8192, 1024), xk(2, 8)),
+                       # the staggered two-slice launches (bits 27-28 = d: mail and first poll inside the K loop)
+                       ((512, 4096, 4096), xw(4, 1, 2) | (1 << 27)), ((512, 4096, 4096), xw(4, 1, 2) | (2 << 27)), ((300, 11008, 4096), xw(4, 1, 2) | (3 << 27)),
+                       ((200, 2048, 4096), xw(4, 1, 2) | (1 << 27))):
     qw, sc, qz = packing.random_mi355x(K, N, 128, dev, gen)
     x = (torch.randn(M, K, device=dev, generator=gen) * 0.5).half()
     plan = kernels.plan_describe(M, K, N, 128, kid)

@@ -13,6 +13,15 @@ Configurations (MB 32-token blocks x PAIRS 32-channel pairs per WAVE; the workgr
                                                                   owns only two 32 x 32 tiles, and an MFMA on the accumulator of the one
                                                                   before last would wait for it)
 
+Staggered K ranges (STAGGERED, "41s": the two-slice 128 x 128 launch, w4a16_xw.hpp ABL & 128).  The (4, 1) stage in two phases inside ONE statement:
+phase 1 = the loop above over N1 = stages - 2 d stages; then, one copy per phase-1 exit, the MAIL (the two blocks the slice does not own, operands
+a2 / a3, rounded to fp16 pairs and stored to the partner's box); phase 2 = a second unrolled ring of `half` stages (MFMAs and B reads of blocks 0, 1
+only, a second accumulator set for odd k16 steps) that runs on in the next slot, and for the slice's last stage the `tail` copies (first POLL of the own
+box in front; no requests, waits or barrier).  Stage t is k tile t + (t < N1 ? ktlo : 0).  Extra operands: kthi = stages | d << 16, rz / vl / sbox (zone
+descriptor, lane offset in a box, the box sent to; the box polled is sbox ^ 0xc000), pl = the sixteen polled dwords; accumulators and pl are physical
+registers (a[0:95], v[222:237]); mail temporaries v196..v220; stamped builds: t2 = the phase change, no clk.  exp & 32: no mail, no polls (gate experiment).
+Written to w4a16_xws_loop.inc beside the main file (staggered_file(): one parametrised statement for all three uses).
+
 Why asm: one wave per SIMD hides ~5 issue slots under a 32-cycle v_mfma_f32_32x32x16_f16 (MI355X_MICROARCH.md, "one wave per SIMD").  hipcc's
 schedule of the (4, 2) work (w4a16_wide_kernel<4, 2>) carries 42 s_nop and 24 s_waitcnt per 64 MFMAs and measures 45.8 clocks per MFMA; this
 loop measures 36.5 [r04, tools/xk_phases.py; the microbenchmark tools/mfma_filler_cost.hip prices the same filler mix at 35.6, bare MFMAs at
@@ -36,15 +45,19 @@ stamped builds: t0, t1 ("=s", 64 bit: s_memrealtime behind the prologue's barrie
 """
 import os
 
-OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "quick_amd", "csrc", "w4a16_xw_loop.inc")
+OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "quick_amd", "csrc", "w4a16_xw_loop.inc")   # (the staggered statement: w4a16_xws_loop.inc beside it)
 
 S_MLO, S_MHI, S_SIXT, S_D400, S_PERM = 52, 53, 54, 55, 56
 S_S, S_N, S_KT, S_XSO, S_KTMAX, S_G, S_KTLO = 57, 58, 59, 60, 65, 66, 67
 S_WSO = [61, 62]
 S_SSO = [63, 64]
 STAMP0, STAMP1, S_TPG, CLK0, CLK1 = 68, 70, 72, 74, 76
+S_N1, S_JMP, S_T2, S_RBOX = 78, 79, 80, 82                 # (staggered slices: stages of phase 1, the k tile jump of a stage, stamp of the phase change)
 S_KTHI, S_WPS, S_SPS, S_K2 = 78, 79, 80, 81     # (256-token tiles: end k tile, pair strides and the row pitch of x, derived from the k tile count)
 RSX, RSW, RSS = "%[rsx]", "%[rsw]", "%[rss]"
+RZ, VL, SBOX = "%[rz]", "%[vl]", "%[sbox]"     # (staggered slices: exchange zone descriptor, the lane's byte offset in a box, the box this slice sends to)
+V_MP, V_MT, V_MK, V_POLL = 196, 212, 220, 222   # packed dwords of the mail [16], fp32 temporaries [8], 0x80008000, the polled granules [16]
+A_BASE = 0                                       # the staggered statement's accumulators are PHYSICAL registers: a[16 i : 16 i + 15] = operand a<i>
 WV, SV, XRD, XDST, KTLO, KTHI, WPS, SPS = "%[wv]", "%[sv]", "%[xrd]", "%[xdst]", "%[ktlo]", "%[kthi]", "%[wps]", "%[sps]"
 
 
@@ -61,8 +74,11 @@ def even(n): return n + (n & 1)
 
 
 class Cfg:
-    def __init__(self, MB, PAIRS, NS, KP, exp=0, KW=1, bar=0):
+    def __init__(self, MB, PAIRS, NS, KP, exp=0, KW=1, bar=0, stag=False):
         self.MB, self.PAIRS, self.NS, self.KP, self.KW = MB, PAIRS, NS, KP, KW
+        # stag: the two-slice launch whose slices finish the blocks they do NOT own a few stages early ("Staggered K ranges" below)
+        self.stag = stag
+        assert not stag or (MB == 4 and PAIRS == 1 and KP == 1 and KW == 1 and not bar)
         # bar = 1: the barrier of a stage sits in FRONT of the last super-step (whose fillers are the first reads of the next stage), so
         # the only counted wait of a stage is "W(s + 1) has landed" (behind X(s + 1)): a load has a whole stage longer to arrive
         self.bar = bar
@@ -83,7 +99,7 @@ class Cfg:
         self.QS = even((self.QW + 1) * PAIRS)
         self.SLOTB = MB * 8192
         self.G = self.SSM * self.NSU       # MFMAs (= gaps) per stage
-        self.NACC = KP * PAIRS * MB
+        self.NACC = KP * PAIRS * MB + (MB // 2 if stag else 0)   # (stag: a second set for the owned blocks' odd k16 steps in phase 2)
         b = 48
         self.VQ = b; b += NS * self.QS
         self.VBF = b; b += 2 * self.NRD * 4
@@ -98,7 +114,8 @@ class Cfg:
         self.VEND = b
         assert self.VEND <= 253, self.VEND
         assert NS * self.SLOTB <= 128 * 1024
-        self.name = "%d%d%s" % (MB, PAIRS, "k" if KW == 2 else "")
+        self.name = "%d%d%s" % (MB, PAIRS, "k" if KW == 2 else ("s" if stag else ""))
+        assert self.VEND <= V_MP or not stag
 
     # registers
     def Q(self, j, what, p=0, t=0):
@@ -110,7 +127,11 @@ class Cfg:
     def BF(self, b, rd): return self.VBF + (b * self.NRD + rd) * 4
     def AF(self, b, ch): return self.VAF + (b * self.NCH + ch) * 4
     def GC(self, c, p, i): return self.VGC + (c * self.PAIRS + p) * 3 + i
-    def ACC(self, kk, p, mt): return "%%[a%d]" % (((kk % self.KP) * self.PAIRS + p) * self.MB + mt)
+    def ACC(self, kk, p, mt, half=False):
+        if self.stag:   # (physical registers; phase 2: even / odd k16 steps of the owned blocks on two sets)
+            i = (mt if kk % 2 == 0 else self.MB + mt) if half else mt
+            return "a[%d:%d]" % (A_BASE + 16 * i, A_BASE + 16 * i + 15)
+        return "%%[a%d]" % (((kk % self.KP) * self.PAIRS + p) * self.MB + mt)
     def XV(self, i): return "%%[xv%d]" % i
 
     def dequant_chain(self, qreg, gc, out, tmp):
@@ -151,9 +172,9 @@ class Cfg:
         ra = self.VRA + kk if off < 65536 else self.VRA2 + kk
         return I(f"ds_read_b128 {v(self.BF(buf, rd), 4)}, {v(ra)} offset:{off % 65536}", "lds", range(self.BF(buf, rd), self.BF(buf, rd) + 4), [ra])
 
-    def mfma(self, kk, p, mt, buf, ch, rd, zero_c):
+    def mfma(self, kk, p, mt, buf, ch, rd, zero_c, half=False):
         a, b = self.AF(buf, ch), self.BF(buf, rd)
-        acc = self.ACC(kk, p, mt)
+        acc = self.ACC(kk, p, mt, half)
         return I(f"v_mfma_f32_32x32x16_f16 {acc}, {v(a, 4)}, {v(b, 4)}, {'0' if zero_c else acc}", "mfma", [], list(range(a, a + 4)) + list(range(b, b + 4)))
 
     def x_piece(self, i, slot, pad=False):
@@ -171,12 +192,48 @@ class Cfg:
             out += [I(f"buffer_load_dword {v(self.Q(j, 'sz', p))}, {SV}, {RSS}, {s(S_SSO[p])} offen", "vmem")]
         return out
 
+    def poll_loads(self):
+        """the first poll of the box the partner sends to: four granules, read through (sc1), into registers the statement hands out; the
+        closing vmcnt(0) of the loop waits for them -- and, loads returning in order behind the stores in front of them, for the mail"""
+        if self.exp & 32: return []
+        return [I(f"buffer_load_dwordx4 {v(V_POLL + 4 * g, 4)}, {VL}, {RZ}, {s(S_RBOX)} offen offset:{1024 * g} sc1", "vmem", range(V_POLL + 4 * g, V_POLL + 4 * g + 4))
+                for g in range(4)]
+
+    def mail(self):
+        """the part of the two blocks this slice does not own (operands a2, a3 = a[32:63]) -> the partner's box: v_accvgpr_read, rounded to
+        fp16 pairs, never the bit pattern 0 (xw_pack of w4a16_xw.hpp), four written-through 16-byte stores (xw_mail_store).  Runs between
+        the phases: the last phase-1 MFMA wrote a3 -- 16 wait states in front of the first read (8-pass MFMA -> VALU read: 10, measured)"""
+        if self.exp & 32: return []
+        out = [I("s_nop 15", "salu"), I(f"v_mov_b32 {v(V_MK)}, 0x80008000", "valu", [V_MK]), I(f"s_xor_b32 {s(S_RBOX)}, {SBOX}, 0xc000", "salu")]
+        for g in range(4):
+            for d in range(4):
+                j = 4 * g + d
+                out += [I(f"v_accvgpr_read_b32 {v(V_MT + 2 * d)}, a{A_BASE + 32 + 2 * j}", "valu", [V_MT + 2 * d]),
+                        I(f"v_accvgpr_read_b32 {v(V_MT + 2 * d + 1)}, a{A_BASE + 33 + 2 * j}", "valu", [V_MT + 2 * d + 1])]
+            for d in range(4):
+                out += [I(f"v_cvt_pk_f16_f32 {v(V_MP + 4 * g + d)}, {v(V_MT + 2 * d)}, {v(V_MT + 2 * d + 1)}", "valu", [V_MP + 4 * g + d], [V_MT + 2 * d, V_MT + 2 * d + 1])]
+            for d in range(4):
+                r = V_MP + 4 * g + d
+                out += [I(f"v_cmp_ne_u32 vcc, 0, {v(r)}", "valu", [], [r]), I("s_nop 1", "salu"), I(f"v_cndmask_b32 {v(r)}, {v(V_MK)}, {v(r)}, vcc", "valu", [r], [r, V_MK])]
+            out += [I("s_nop 0", "salu"),
+                    I(f"buffer_store_dwordx4 {v(V_MP + 4 * g, 4)}, {VL}, {RZ}, {SBOX} offen offset:{1024 * g} sc1", "vmem", [], range(V_MP + 4 * g, V_MP + 4 * g + 4))]
+        # (the packed dwords keep their registers to the end of the statement: nothing overwrites a store's data behind it, DESIGN.md 5.6)
+        return pad_deps(out)
+
     def offsets(self, ahead):
         """scalar offsets of stage S_S + ahead (clamped to the last k tile of the slice: past the end the loads replay it, nobody uses them)"""
-        out = [
-            I(f"s_add_u32 {s(S_KT)}, {s(S_S)}, {ahead}", "salu"),
-            I(f"s_add_u32 {s(S_KT)}, {s(S_KT)}, {s(S_KTLO)}", "salu"),
-            I(f"s_min_u32 {s(S_KT)}, {s(S_KT)}, {s(S_KTMAX)}", "salu"),
+        out = [I(f"s_add_u32 {s(S_KT)}, {s(S_S)}, {ahead}", "salu")]
+        if self.stag:
+            # stage t of a staggered slice (clamped to its last stage) is k tile t + (t < N1 ? ktlo : 0): phase 1 starts at ktlo, phase 2 of
+            # BOTH slices covers the k tiles [N1, N1 + 2 d) -- for slice 1 (ktlo = N1 + 2 d) that is the jump back, wherever the stream crosses it
+            out += [I(f"s_min_u32 {s(S_KT)}, {s(S_KT)}, {s(S_KTMAX)}", "salu"),
+                    I(f"s_cmp_lt_u32 {s(S_KT)}, {s(S_N1)}", "salu"),
+                    I(f"s_cselect_b32 {s(S_JMP)}, {s(S_KTLO)}, 0", "salu"),
+                    I(f"s_add_u32 {s(S_KT)}, {s(S_KT)}, {s(S_JMP)}", "salu")]
+        else:
+            out += [I(f"s_add_u32 {s(S_KT)}, {s(S_KT)}, {s(S_KTLO)}", "salu"),
+                    I(f"s_min_u32 {s(S_KT)}, {s(S_KT)}, {s(S_KTMAX)}", "salu")]
+        out += [
             I(f"s_lshl_b32 {s(S_XSO)}, {s(S_KT)}, 8", "salu"),
             I(f"s_lshl_b32 {s(S_WSO[0])}, {s(S_KT)}, 10", "salu"),
             I(f"s_lshr_b32 {s(S_G)}, {s(S_KT)}, {s(S_TPG)}", "salu"),
@@ -207,8 +264,11 @@ class Cfg:
                 dq.append(c[i])
         return reads, dq
 
-    def superstep(self, J, u, peel=False):
-        """the SSM MFMAs of super-step u of stage J, each followed by its fillers"""
+    def superstep(self, J, u, peel=False, half=False, tail=False):
+        """the SSM MFMAs of super-step u of stage J, each followed by its fillers.  half (phase 2 of a staggered slice): the same stage with
+        the MFMAs and B reads of blocks MB / 2 .. left out -- four MFMAs, each followed by the fillers of two gaps; tail: the LAST stage of
+        the slice -- the first poll of the partner's box in front, no requests, no counted waits, no barrier (what they would fetch, nobody
+        uses; everything this stage uses was waited for two stages ago), and nothing prepared for a stage that does not exist"""
         G, NS, SSM = self.G, self.NS, self.SSM
         last = u == self.NSU - 1
         nJ, nu = ((J + 1) % NS, 0) if last else (J, u + 1)
@@ -276,25 +336,55 @@ class Cfg:
         else: per_gap = [6, 6, 6, 6, 7, 7, 7, 7]
         assert sum(per_gap) == nd
         out, di, waited, zeroed = [], 0, -1, set()
-        for g in range(SSM):
+        kept = [rd for rd in range(self.NRD) if not half or rd % self.MB < self.MB // 2]   # the reads the super-step before issued for this one
+        issued = 0
+        def emit_mfma(g):
+            nonlocal waited
             st, gi = g // self.MPS, g % self.MPS
             p, mt = gi // self.MB, gi % self.MB
             kk = u * self.SS + st
             rd, ch = st * self.MB + mt, st * self.PAIRS + p
             if rd > waited and not peel:
-                out.append(I(f"s_waitcnt lgkmcnt({(self.NRD - 1 - rd) + min(g, self.NRD)})", "wait"))
+                # (entering phase 2 the last phase-1 super-step has read all four blocks: the count for four reads waits for more, never less)
+                out.append(I(f"s_waitcnt lgkmcnt({(len(kept) - 1 - kept.index(rd)) + issued})", "wait"))
                 waited = rd
-            acc = self.ACC(kk, p, mt)
-            out.append(self.mfma(kk, p, mt, buf, ch, rd, peel and acc not in zeroed))
+            acc = self.ACC(kk, p, mt, half)
+            out.append(self.mfma(kk, p, mt, buf, ch, rd, peel and acc not in zeroed, half))
             zeroed.add(acc)
-            if g < self.NRD:
+        def emit_fillers(g):
+            nonlocal di, issued
+            if tail and last:
+                return
+            if g < self.NRD and g in kept:
                 out.append(reads[g])
-            out += pre[g]
-            out += dq[di:di + per_gap[g]]
+                issued += 1
+            out.extend(pre[g])
+            out.extend(dq[di:di + per_gap[g]])
             di += per_gap[g]
-            out += extras[g]
-        assert di == nd
-        if self.exp:
+            out.extend(extras[g])
+        if tail and u == 0:
+            out.extend(self.poll_loads())
+        if half:
+            for k, g in enumerate(kept):   # (NRD == SSM: the kept reads' indices are the kept MFMAs' gaps)
+                emit_mfma(g)
+                emit_fillers(2 * k)
+                emit_fillers(2 * k + 1)
+        else:
+            for g in range(SSM):
+                emit_mfma(g)
+                emit_fillers(g)
+        assert di == nd or (tail and last)
+        if tail:
+            gcregs = set(self.GC(1 - J % 2, p, i) for p in range(self.PAIRS) for i in range(3)) | set(self.VZT + p for p in range(self.PAIRS))
+            def keep_tail(i):
+                t = i.text
+                if i.kind == "vmem" and "sc1" not in t: return False
+                if t.startswith("s_waitcnt vmcnt") or t.startswith("s_add_u32 m0") or t == "s_barrier": return False
+                if i.kind == "salu" and not t.startswith("s_nop"): return False            # (stage counter and offsets of requests that are not made)
+                if i.kind == "valu" and i.w and i.w <= gcregs: return False                # (group constants of the stage behind the last)
+                return True
+            out = [i for i in out if keep_tail(i)]
+        if self.exp & 31:
             def keep(i):
                 t = i.text
                 if (self.exp & 1) and t == "s_barrier": return False
@@ -361,7 +451,13 @@ def build(c, stamped):
             pro += [I(f"v_add_u32 {v(t)}, {16 * i}, %[xr]", "valu", [t]),
                     I(f"v_min_u32 {v(t)}, %[mlast], {v(t)}", "valu", [t], [t]),
                     I(f"v_mad_u32_u24 {v(c.VX + i)}, {v(t)}, {s(S_K2)}, %[xc]", "valu", [c.VX + i], [t])]
-    pro += [I(f"s_sub_u32 {s(S_N)}, {kthi}, {s(S_KTLO)}", "salu"), I(f"s_sub_u32 {s(S_KTMAX)}, {kthi}, 1", "salu")]
+    if c.stag:
+        # kthi = stages of the slice (both phases) | d << 16; N1 = stages - 2 d of them are phase 1; S_KTMAX is the last STAGE here
+        pro += [I(f"s_and_b32 {s(S_N)}, {KTHI}, 0xffff", "salu"), I(f"s_lshr_b32 {s(S_JMP)}, {KTHI}, 16", "salu"),
+                I(f"s_lshl_b32 {s(S_JMP)}, {s(S_JMP)}, 1", "salu"), I(f"s_sub_u32 {s(S_N1)}, {s(S_N)}, {s(S_JMP)}", "salu"),
+                I(f"s_sub_u32 {s(S_KTMAX)}, {s(S_N)}, 1", "salu")]
+    else:
+        pro += [I(f"s_sub_u32 {s(S_N)}, {kthi}, {s(S_KTLO)}", "salu"), I(f"s_sub_u32 {s(S_KTMAX)}, {kthi}, 1", "salu")]
     # the ring and the queue as NS - 1 stages of the steady state would have left them: X(q) W(q), q = 0 .. NS - 2
     for q in range(c.NS - 1):
         pro += c.offsets(q)
@@ -369,6 +465,8 @@ def build(c, stamped):
         pro += c.w_loads(q)
     pro += c.offsets(c.NS - 1)   # what stage 0 itself issues
     pro += [I(f"v_mov_b32 {v(c.VMAGIC)}, 0x64006400", "valu", [c.VMAGIC])]
+    if c.stag:   # the owned blocks' second set starts from zero (phase 2 is entered in whichever copy phase 1 ends: nothing of it can be peeled)
+        pro += [I(f"v_accvgpr_write_b32 a{A_BASE + 16 * c.MB + r}, 0", "valu") for r in range(16 * (c.MB // 2))]
     for kk in range(c.KST):   # (KW = 2: the wave's j-th step is k16 step 2 j + parity of the stage; xrd carries the parity)
         pro += [I(f"v_xor_b32 {v(c.VRA + kk)}, {(kk * c.KW) << 5}, {XRD}", "valu", [c.VRA + kk])]
     for kk in range(c.KST):
@@ -403,8 +501,54 @@ def build(c, stamped):
             text += emit(st)
             nins += len(st)
             prev = st
+        if c.stag:
+            # phase 1 ends behind stage N1 - 1, in whichever copy that is (stage t always runs in copy t % NS)
+            text += '  "s_cmp_ge_u32 %s, %s\\n\\t"\n' % (s(S_S), s(S_N1))
+            text += ('  "s_cbranch_scc1 .Lxw_m%d_%%=\\n\\t"\n' % J) if J < c.NS - 1 else '  "s_cbranch_scc0 .Lxw_loop_%=\\n\\t"\n'
+            continue
         text += '  "s_cmp_ge_u32 %s, %s\\n\\t"\n' % (s(S_S), s(S_N))
         text += '  "s_cbranch_scc1 .Lxw_done_%=\\n\\t"\n' if J < c.NS - 1 else '  "s_cbranch_scc0 .Lxw_loop_%=\\n\\t"\n'
+    if c.stag:
+        # ---- between the phases: the mail leaves, then on into the next copy of the phase-2 ring.  One copy of the mail per way in (the
+        # control flow stays exact: tools/vmcnt_lint.py walks every edge); phase 2 has 2 d >= 2 stages, so never straight into the tail.
+        ml = c.mail()
+        check(c.superstep(c.NS - 1, c.NSU - 1)[-40:] + ml, "mail")
+        for J in [c.NS - 1] + list(range(c.NS - 1)):   # (the last copy of phase 1 falls into its mail)
+            text += '  ".Lxw_m%d_%%=:\\n\\t"\n' % J
+            if stamped:
+                text += '  "s_memrealtime s[%d:%d]\\n\\t"\n' % (S_T2, S_T2 + 1)
+            text += emit(ml)
+            nins += len(ml)
+            text += '  "s_branch .Lxw_p%d_%%=\\n\\t"\n' % ((J + 1) % c.NS)
+        for J in range(c.NS):
+            text += '  ".Lxw_p%d_%%=:\\n\\t"\n' % J
+            for u in range(c.NSU):
+                st = c.superstep(J, u, half=True)
+                check((ml if J == 0 and u == 0 else prev)[-40:] + st, f"phase 2 J{J} u{u}")
+                if u == 0:
+                    check(c.superstep((J - 1) % c.NS, c.NSU - 1)[-40:] + ml[-40:] + st, "phase change")
+                text += emit(st)
+                nins += len(st)
+                prev = st
+            # one stage left: the tail copy of the next slot
+            text += '  "s_cmp_ge_u32 %s, %s\\n\\t"\n' % (s(S_S), s(S_KTMAX))
+            text += '  "s_cbranch_scc1 .Lxw_q%d_%%=\\n\\t"\n' % ((J + 1) % c.NS)
+            if J == c.NS - 1:
+                text += '  "s_branch .Lxw_p0_%=\\n\\t"\n'
+        check(c.superstep(c.NS - 1, c.NSU - 1, half=True)[-40:] + c.superstep(0, 0, half=True), "phase 2 wrap")
+        for J in range(c.NS):
+            text += '  ".Lxw_q%d_%%=:\\n\\t"\n' % J
+            prev = c.superstep((J - 1) % c.NS, c.NSU - 1, half=True)
+            for u in range(c.NSU):
+                st = c.superstep(J, u, half=True, tail=True)
+                check(prev[-40:] + st, f"tail J{J} u{u}")
+                if u == 0:
+                    check(c.superstep((J - 1) % c.NS, c.NSU - 1)[-40:] + ml[-40:] + st, "phase change into the tail")
+                text += emit(st)
+                nins += len(st)
+                prev = st
+            if J < c.NS - 1:
+                text += '  "s_branch .Lxw_done_%=\\n\\t"\n'
     check(c.superstep(c.NS - 1, c.NSU - 1)[-40:] + c.superstep(0, 0), "wrap")
     text += '  ".Lxw_done_%=:\\n\\t"\n'
     if stamped:
@@ -412,8 +556,10 @@ def build(c, stamped):
     text += '  "s_waitcnt vmcnt(0) lgkmcnt(0)\\n\\t"\n'
     if stamped:
         text += '  "s_mov_b64 %%[t0], s[%d:%d]\\n\\t"\n  "s_mov_b64 %%[t1], s[%d:%d]\\n\\t"\n' % (STAMP0, STAMP0 + 1, STAMP1, STAMP1 + 1)
-        if not c.big:
+        if not c.big and not c.stag:
             text += '  "s_sub_u32 %%[clk], s%d, s%d\\n\\t"\n' % (CLK1, CLK0)
+        if c.stag:
+            text += '  "s_mov_b64 %%[t2], s[%d:%d]\\n\\t"\n' % (S_T2, S_T2 + 1)
     text += '  "s_nop 15\\n\\t"\n  "s_nop 7"\n'   # the last MFMAs' results -> whoever reads the accumulators next
     return text, nins
 
@@ -421,16 +567,27 @@ def build(c, stamped):
 def run_macro(c):
     """the whole asm statement: names of the kernel's variables (accr[], b, xrd, xdst, kt_lo, kt_hi; stamped: t0, t1, clk; 256-token tiles:
     xr = first row of the lane's piece 0, xc = its swizzled 16-byte chunk, kt_hi carries K / 128 in its upper half, m_last = M - 1)"""
-    outs = ", ".join('[a%d] "=&a"(accr[%d])' % (i, i) for i in range(c.NACC))
+    if c.stag:
+        # physical registers: the mail reads single accumulator registers and the polls load quarters of one 16-dword operand, and an asm
+        # operand cannot be indexed; "&": no input may share them
+        outs = ", ".join('[a%d] "=&{a[%d:%d]}"(accr[%d])' % (i, A_BASE + 16 * i, A_BASE + 16 * i + 15, i) for i in range(c.NACC))
+        if not c.exp & 32:
+            outs += ', [pl] "=&{v[%d:%d]}"(pollv)' % (V_POLL, V_POLL + 15)
+    else:
+        outs = ", ".join('[a%d] "=&a"(accr[%d])' % (i, i) for i in range(c.NACC))
     ins = ['[rsx] "s"(b.x)', '[rsw] "s"(b.w)', '[rss] "s"(b.s)']
     if c.big:
         ins += ['[xr] "v"(xr)', '[xc] "v"(xc)']
     else:
         ins += ['[xv%d] "v"(b.x_voff[%d])' % (i, i) for i in range(c.NX)]
     ins += ['[wv] "v"(b.w_voff)', '[sv] "v"(b.s_voff)', '[xrd] "v"(xrd)', '[xdst] "s"(xdst)', '[ktlo] "s"(kt_lo)', '[kthi] "s"(kt_hi)']
-    ins += ['[mlast] "s"(m_last)'] if c.big else ['[wps] "s"(b.w_pstride)', '[sps] "s"(b.s_pstride)']
-    cl = ['"memory"', '"scc"', '"m0"'] + ['"v%d"' % r for r in range(48, c.VEND)] + ['"s%d"' % r for r in range(52, 82 if c.big else 78)]
-    stamps = '[t0] "=&s"(t0), [t1] "=&s"(t1)' + ('' if c.big else ', [clk] "=&s"(clk)')
+    ins += ['[mlast] "s"(m_last)'] if c.big else ([] if c.stag else ['[wps] "s"(b.w_pstride)', '[sps] "s"(b.s_pstride)'])   # (one pair: no pair strides)
+    if c.stag and not c.exp & 32:
+        ins += ['[rz] "s"(rz)', '[vl] "v"(vlane)', '[sbox] "s"(sbox)']
+    cl = ['"memory"', '"scc"', '"m0"'] + ['"v%d"' % r for r in range(48, c.VEND)] + ['"s%d"' % r for r in range(52, 83 if c.stag else (82 if c.big else 78))]
+    if c.stag:
+        cl += ['"vcc"'] + ['"v%d"' % r for r in range(V_MP, V_POLL)]
+    stamps = '[t0] "=&s"(t0), [t1] "=&s"(t1)' + ('' if c.big or c.stag else ', [clk] "=&s"(clk)') + (', [t2] "=&s"(t2)' if c.stag else '')
     body = "#define QA_XW_RUN_%s() asm volatile(QA_XW_ASM_%s : %s : %s : %s)\n" % (c.name, c.name, outs, ", ".join(ins), ", ".join(cl))
     body += ("#define QA_XW_RUN_STAMPED_%s() asm volatile(QA_XW_ASM_STAMPED_%s : %s, %s : %s : %s)\n"
              % (c.name, c.name, outs, stamps, ", ".join(ins), ", ".join(cl)))
@@ -438,6 +595,7 @@ def run_macro(c):
 
 
 CONFIGS = [Cfg(4, 2, 4, 1), Cfg(4, 1, 4, 1), Cfg(2, 1, 8, 2), Cfg(8, 2, 2, 1, bar=1)]
+STAGGERED = [Cfg(4, 1, 4, 1, stag=True)]   # the two-slice 128 x 128 launch with staggered K ranges ("41s"): the (4, 1) stage in two phases, mail and first poll inside
 # Tried and not kept [r04, profiles/r04_loop_variants.txt] -- the options stay in the generator for the record:
 #   Cfg(4, 2, 4, 1, KW=2)   128 x 128 tile of (4, 2)-shaped waves, the two wave pairs splitting the k16 steps of a stage by parity (half the
 #                           B reads per MFMA of (4, 1)): 40.6-41.3 clocks per MFMA, the same as (4, 1)'s 41.3-41.6 -- what the 128 x 128
@@ -447,6 +605,10 @@ CONFIGS = [Cfg(4, 2, 4, 1), Cfg(4, 1, 4, 1), Cfg(2, 1, 8, 2), Cfg(8, 2, 2, 1, ba
 EXPERIMENTS = [(2, 1, 8, 2, e) for e in (1, 2, 4, 8, 15)] + [(4, 1, 4, 1, e) for e in (1, 2, 4, 8)]
 
 
+def cont(text):
+    return "".join(l + " \\\n" for l in text.rstrip("\n").split("\n")) + "\n"
+
+
 def main():
     body = ("// GENERATED by tools/gen_xw_loop.py -- do not edit.  The K loops of w4a16_xw_kernel, one inline-asm statement per tile shape\n"
             "// (operands and register plan: the generator's docstring and w4a16_xw.hpp).\n")
@@ -454,7 +616,7 @@ def main():
         for stamped in (False, True):
             text, n = build(c, stamped)
             body += "#define QA_XW_ASM_%s%s \\\n" % ("STAMPED_" if stamped else "", c.name)
-            body += "".join(l + " \\\n" for l in text.rstrip("\n").split("\n")) + "\n"
+            body += cont(text)
         body += run_macro(c)
         print("config (%d, %d): %d instructions, VGPRs v48..v%d, ring / queue of %d, LDS %d KiB" % (c.MB, c.PAIRS, n, c.VEND - 1, c.NS, c.NS * c.SLOTB // 1024))
     body += "#ifdef QUICK_AMD_TOOLS\n"
@@ -463,12 +625,61 @@ def main():
         text, n = build(c, True)
         nm = "%s_E%d" % (c.name, e)
         body += "#define QA_XW_ASM_STAMPED_%s \\\n" % nm
-        body += "".join(l + " \\\n" for l in text.rstrip("\n").split("\n")) + "\n"
+        body += cont(text)
         body += run_macro(c).split("\n")[1].replace("QA_XW_RUN_STAMPED_%s" % c.name, "QA_XW_RUN_STAMPED_%s" % nm).replace("QA_XW_ASM_STAMPED_%s " % c.name, "QA_XW_ASM_STAMPED_%s " % nm) + "\n"
     body += "#endif\n"
     with open(OUT, "w") as f:
         f.write(body)
     print("wrote", OUT)
+    out2 = os.path.join(os.path.dirname(OUT), "w4a16_xws_loop.inc")
+    with open(out2, "w") as f:
+        f.write(staggered_file())
+    print("wrote", out2)
+
+
+def staggered_file():
+    """w4a16_xws_loop.inc: the staggered statement ONCE, as a function-like macro whose arguments are the pieces its three uses differ in --
+    the stamps (T0 behind the prologue's barrier, T2 at the phase change, T1 / TE at the end), the MAIL between the phases (four copies, one
+    per phase-1 exit) and the first POLL in front of the last stage (four copies).  Product: mail and polls, no stamps; phase-stamp builds: all;
+    the gate experiment of DESIGN.md 9 (tools builds, exchange compiled out): stamps only.  Every use is checked here to be, string for string, what
+    build() writes for it."""
+    c, ce = STAGGERED[0], Cfg(4, 1, 4, 1, exp=32, stag=True)
+    full = {"plain": build(c, False)[0], "stamped": build(c, True)[0], "gate": build(ce, True)[0]}
+    n = build(c, False)[1]
+    lit = lambda lines: "".join('  "%s\\n\\t"\n' % l for l in lines)
+    pieces = {
+        "T0": lit(["s_memrealtime s[%d:%d]" % (STAMP0, STAMP0 + 1), "s_memtime s[%d:%d]" % (CLK0, CLK0 + 1), "s_waitcnt lgkmcnt(0)"]),
+        "T2": lit(["s_memrealtime s[%d:%d]" % (S_T2, S_T2 + 1)]),
+        "MAIL": emit(c.mail()),
+        "POLL": emit(c.poll_loads()),
+        "T1": lit(["s_memrealtime s[%d:%d]" % (STAMP1, STAMP1 + 1), "s_memtime s[%d:%d]" % (CLK1, CLK1 + 1)]),
+        "TE": lit(["s_mov_b64 %%[t0], s[%d:%d]" % (STAMP0, STAMP0 + 1), "s_mov_b64 %%[t1], s[%d:%d]" % (STAMP1, STAMP1 + 1), "s_mov_b64 %%[t2], s[%d:%d]" % (S_T2, S_T2 + 1)]),
+    }
+    order = ["T0", "T2", "MAIL", "POLL", "T1", "TE"]
+    tmpl = full["stamped"]
+    for k, cnt in (("MAIL", c.NS), ("POLL", c.NS), ("T0", 1), ("T2", c.NS), ("T1", 1), ("TE", 1)):
+        assert tmpl.count(pieces[k]) == cnt, (k, tmpl.count(pieces[k]))
+        tmpl = tmpl.replace(pieces[k], "  %s\n" % k)
+    uses = {"plain": {"MAIL", "POLL"}, "stamped": set(order), "gate": {"T0", "T2", "T1", "TE"}}
+    for name, on in uses.items():
+        t = tmpl
+        for k in order:
+            t = t.replace("  %s\n" % k, pieces[k] if k in on else "")
+        assert t == full[name], name
+    body = ("// GENERATED by tools/gen_xw_loop.py -- do not edit.  The K loop of the STAGGERED two-slice 128 x 128 launch (w4a16_xw.hpp, ABL & 128): one\n"
+            "// inline-asm statement, written once; its uses differ in the macro arguments (stamps, mail, first poll) -- the generator's docstring.\n")
+    names = {"T0": "QA_XWS_T0", "T2": "QA_XWS_T2", "MAIL": "QA_XWS_MAIL", "POLL": "QA_XWS_POLL", "T1": "QA_XWS_T1", "TE": "QA_XWS_TE"}
+    for k in order:
+        body += "#define %s \\\n" % names[k] + cont(pieces[k])
+    body += "#define QA_XWS_BODY(%s) \\\n" % ", ".join(order) + cont(tmpl)
+    arg = lambda on: ", ".join(names[k] if k in on else "" for k in order)
+    body += "#define QA_XW_ASM_41s QA_XWS_BODY(%s)\n" % arg(uses["plain"])
+    body += "#define QA_XW_ASM_STAMPED_41s QA_XWS_BODY(%s)\n" % arg(uses["stamped"])
+    body += run_macro(c)
+    body += "#ifdef QUICK_AMD_TOOLS\n#define QA_XW_ASM_STAMPED_41s_E32 QA_XWS_BODY(%s)\n" % arg(uses["gate"])
+    body += run_macro(ce).split("\n")[1].replace("QA_XW_RUN_STAMPED_41s", "QA_XW_RUN_STAMPED_41s_E32").replace("QA_XW_ASM_STAMPED_41s ", "QA_XW_ASM_STAMPED_41s_E32 ") + "\n#endif\n"
+    print("config (4, 1) staggered: %d instructions, VGPRs v48..v%d + mail / poll v%d..v%d, ring / queue of %d" % (n, c.VEND - 1, V_MP, V_POLL + 15, c.NS))
+    return body
 
 
 if __name__ == "__main__":

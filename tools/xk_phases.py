@@ -1,6 +1,8 @@
 """Diagnostic: where an exchange-K launch spends its time (needs the QUICK_AMD_TOOLS library: `python -m quick_amd.build --tools`,
 QUICK_AMD_LIB_OVERRIDE=tools/bin/libquick_amd_tools.so).  Per-wave s_memrealtime stamps at the phase boundaries.
-    python tools/xk_phases.py [--kernel ID] [MxKxN ...]        ID: QUICK_KERNEL_XK | mb << 4 | slices << 8 ..., default 128-token tiles"""
+    python tools/xk_phases.py [--kernel ID] [MxKxN ...]        ID: QUICK_KERNEL_XK | mb << 4 | slices << 8 ..., default 128-token tiles
+Kernel-id bits 27-28 on the two-slice 128 x 128 four-wave launch (the staggered K ranges): the K loop's phase 2 is printed on its own; with --abl 20 (no exchange)
+the loop runs without mail and polls -- the gate experiment of DESIGN.md 9.1."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -56,6 +58,11 @@ for spec in (args or ["512x4096x4096"]):
     kc = np.mean([c.mean() for c in cycs])
     kl = max(kl, 1e-9)
     print(f"   K loop: {kc:.0f} shader clocks per wave in {kl:.2f} us = {kc / kl / 1000:.3f} GHz")
+    if (kid & 15) == 5 and (kid >> 27) & 3:   # the staggered two-slice launch: word 7 is the stamp of the phase change
+        p2 = np.array([[(d[:, 2] - g.astype(np.float64) / 100.0).mean(), (d[:, 2] - g.astype(np.float64) / 100.0).min(), (d[:, 2] - g.astype(np.float64) / 100.0).max()]
+                       for d, g in zip(acc, segs)]).mean(0)
+        print(f"   of the K loop, phase 2 (owned blocks only, stagger {(kid >> 27) & 3}): mean {p2[0]:.2f} us   min {p2[1]:.2f}   max {p2[2]:.2f}")
+        continue
     loc = np.mean([g.astype(np.float64).mean() for g in segs])
     print(f"   word 7 (XW: share of waves whose tile sat behind one L2): {loc:.3f}")
     sw = np.mean([(g >> np.uint64(32)).astype(np.float64).mean() for g in segs])

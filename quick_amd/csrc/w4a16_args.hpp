@@ -1,5 +1,5 @@
 // Kernel argument block and the helpers every W4A16 kernel family shares: in-kernel span stamps and the K-split slabs
-// ("last arriver finishes the tile").  Included by every translation unit that defines kernels (w4a16_gemm.hip, w4a16_xk.hip).
+// ("last arriver finishes the tile").  Included by every translation unit that defines kernels (w4a16_skinny.hip, w4a16_tiled.hip, w4a16_wide.hip, w4a16_xk.hip, ...).
 #pragma once
 #include "w4a16_common.hpp"
 

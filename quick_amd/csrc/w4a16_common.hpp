@@ -105,7 +105,7 @@ __device__ __forceinline__ half8_t dequant8(uint32_t q, const GroupQ& g) {
 // One packed dword -> eight fp16 values, the weight still carrying its bias: (1024 + w) for k % 8 in {0,1,4,5}, where
 // the nibble lands in the mantissa of 1024.0 (ulp 1), and (64 + w) for k % 8 in {2,3,6,7}, where it lands four bits
 // higher in the mantissa of 64.0 (ulp 1/16).  Exact, 5 VALU ops; the deferred-zero kernel feeds this to the MFMA and
-// removes bias, zero point and scale once per group in fp32 (see w4a16_gemm.hip).
+// removes bias, zero point and scale once per group in fp32 (see w4a16_skinny.hip).
 __device__ __forceinline__ half8_t biased8(uint32_t q) {
   const uint32_t m1024 = 0x64006400u, m64 = 0x54005400u;
   const uint32_t q8 = q >> 8;

@@ -1,7 +1,7 @@
 // "Lean" small-M kernel (r05): 1..16 tokens, one 16-channel tile per workgroup, the waves split K.
 //
 // Replaces, for the decode regime, the reference's _m1n128k32 / _m16n128k32 kernels (csrc/gemm_cuda_quick.cu:1199-1290).
-// Same arithmetic as the deferred-zero table flavour of the skinny kernel (w4a16_gemm.hip, skinny_compute_dz): x is the A
+// Same arithmetic as the deferred-zero table flavour of the skinny kernel (w4a16_skinny.hip, skinny_compute_dz): x is the A
 // operand of v_mfma_f32_16x16x32_f16, the still biased weights (biased8) the B operand, bias / zero point / scale leave once
 // per 128-k unit in fp32.  What is new is the ORDER of the launch, built around the fact that vector-memory loads return in
 // issue order (vmcnt counts in order):
@@ -19,7 +19,7 @@
 //   * one barrier, in front of the reduction.
 //
 // G % 128 == 0.  RMSNorm prologue: the rows' sums of squares from the LDS copy of x (one barrier), then x normalised in place with
-// quick_rmsnorm_f16's rounding points, fp16(fp16(x * rstd) * weight) (rms_scale8, as the fragment flavour of w4a16_gemm.hip).
+// quick_rmsnorm_f16's rounding points, fp16(fp16(x * rstd) * weight) (rms_scale8, as the fragment flavour of w4a16_skinny.hip).
 // Epilogues: bias, residual (added to the rounded product), SiLU * mul as in skinny_finish.
 #pragma once
 #include "w4a16_args.hpp"

@@ -1,5 +1,5 @@
 // Host-side interface of the GEMM planner (w4a16_plan.hip): what a W4A16 launch runs -- family, tile, K split, workspace -- for a shape
-// and a kernel id.  Used by the launchers and entry points in w4a16_gemm.hip.
+// and a kernel id.  Used by the families' launchers (w4a16_skinny.hip, w4a16_tiled.hip, w4a16_wide.hip) and the dispatcher and entry points in w4a16_gemm.hip.
 #pragma once
 #include <algorithm>
 #include <cstddef>

@@ -293,7 +293,7 @@ __device__ __forceinline__ void xk_way_out(const GemmArgs& a, const XkTile& t, f
   // part `ks_part` of this wave (P registers, flattened register ks_part * P + f = (block j, accumulator register r): token
   // m0 + ((wk * HB + j) * 32 + rho), channels 128 nb + 32 wn + 8 (r / 4) + 4 h + r % 4) straight from the registers, GR channels per store
   auto store_direct = [&](int ks_part, const float (&v)[P]) __attribute__((always_inline)) {
-    if (a.silu_mul) {   // (only where a part is whole 32-token blocks: make_plan / run_gemm)
+    if (a.silu_mul) {   // (only where a part is whole 32-token blocks: make_plan / run_xk)
       if constexpr (P % 16 == 0) {
 #pragma unroll
         for (int jj = 0; jj < P / 16; ++jj) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "w4a16_args.hpp"
+#include "w4a16_launch.hpp"
 
 namespace quick_amd {
 
@@ -20,6 +21,6 @@ constexpr size_t kXkZoneBytesHost = (size_t)16 << 20;  // == kXkZoneBytes (w4a16
 // the (nbuf, wd) the library ships for a tile size
 XkConfig xk_default_config(int mb, int s);
 // false: no instantiation for this configuration / group mode
-bool xk_launch(const XkConfig& c, const GemmArgs& a, int workgroups, hipStream_t st, hipEvent_t start, hipEvent_t stop);
+bool xk_launch(const XkConfig& c, const GemmArgs& a, int workgroups, const Launch& L);
 
 }  // namespace quick_amd

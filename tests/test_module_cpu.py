@@ -143,6 +143,19 @@ def test_c_abi_library_exports_every_declared_symbol():
     assert _lib.load().quick_w4a16_workspace_bytes_ex(512, 4096, 4096, 128, 4, 0) == 65536 + (16 << 20)
 
 
+def test_span_and_profile_refuse_bad_arguments_before_any_gpu_work():
+    """quick_w4a16_gemm_span / _profile: no launches, more span launches than the stamp buffer is sized for (256), no weight set and no
+    result array are QUICK_ERR_INVALID_ARGUMENT, answered before anything touches the GPU (this test runs without one)."""
+    lib = _lib.load()
+    out = (ctypes.c_float * 4)()
+    def call(fn, n_sets, iters, res):
+        return fn(None, None, None, None, n_sets, None, None, 0, 1, 256, 256, 128, 0, 0, iters, res, None)
+    for fn, text in ((lib.quick_w4a16_gemm_span, "bad span arguments"), (lib.quick_w4a16_gemm_profile, "bad profile arguments")):
+        for n_sets, iters, res in ((1, 0, out), (0, 2, out), (1, 2, None)):
+            assert call(fn, n_sets, iters, res) == 1 and text in _lib.last_error(), (text, n_sets, iters, _lib.last_error())
+    assert call(lib.quick_w4a16_gemm_span, 1, 257, out) == 1 and "1..256" in _lib.last_error()
+
+
 def test_product_library_has_no_timing_experiments():
     """Kernel-id bits 16-20 select ablation builds (wrong results on purpose) and phase stamps: a QUICK_AMD_TOOLS build only.
     The product library rejects them before any GPU work and exports no such kernels."""

@@ -20,7 +20,7 @@ while args and args[0] in ("--kernel", "--abl", "--env-abl"):
         os.environ["QUICK_XK_ABL"] = args[1]
     else:
         abl = int(args[1], 0)   # 16 stamps only, 17 loads only, 18 no loads, 19 no loads + no B reads, 20 no exchange, 21 no loads + no dequant,
-    args = args[2:]             # 22 MFMAs + barrier, 23 no loads + no barrier, 24 MFMAs only (w4a16_gemm.hip, run_gemm)
+    args = args[2:]             # 22 MFMAs + barrier, 23 no loads + no barrier, 24 MFMAs only (w4a16_gemm.hip, run_xk)
 DBG = 4096 * 8 * 64
 for spec in (args or ["512x4096x4096"]):
     M, K, N = (int(v) for v in spec.split("x"))

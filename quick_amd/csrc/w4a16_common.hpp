@@ -45,26 +45,12 @@ __device__ __forceinline__ uint32_t as_u32(half2_t h) { return __builtin_bit_cas
 // those pairs only for instructions it knows to be VALU, and a build whose register allocation put such an asm next to the wrong MFMA computed tiles
 // wrong (the unconditional-request chunk loop of r05, DESIGN.md 9.6: cured by this form, by a trailing s_nop inside the asm, and by
 // -amdgpu-waitcnt-forcezero; not by any wait on memory).  Now the two EMPTY asm statements only hide the constants' values; the instruction is hipcc's
-// own, with its hazards seen.  QA_ANDOR_ASM=1 (A/B builds) restores the asm form.
+// own, with its hazards seen.  tools/patches/and_or_asm_forms.patch (A/B builds) restores the asm form and its two s_nop variants.
 __device__ __forceinline__ uint32_t and_or(uint32_t a, uint32_t mask, uint32_t orv) {
-#if defined(QA_ANDOR_ASM) && QA_ANDOR_ASM == 1
-  uint32_t r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(mask), "v"(orv));
-  return r;
-#elif defined(QA_ANDOR_ASM) && QA_ANDOR_ASM == 2   // (... with a wait state behind it: cures the r05 build; ... == 3, in front of it: does not)
-  uint32_t r;
-  asm("v_and_or_b32 %0, %1, %2, %3\n\ts_nop 0" : "=v"(r) : "v"(a), "s"(mask), "v"(orv));
-  return r;
-#elif defined(QA_ANDOR_ASM) && QA_ANDOR_ASM == 3
-  uint32_t r;
-  asm("s_nop 0\n\tv_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(mask), "v"(orv));
-  return r;
-#else
   uint32_t m = mask, o = orv;
   asm("" : "+s"(m));
   asm("" : "+v"(o));
   return (a & m) | o;
-#endif
 }
 
 // Per-(group, output channel) dequantisation constants held by a lane.

@@ -26,11 +26,9 @@
 
 namespace quick_amd {
 
-#ifndef QA_LEAN_WAUX
-#define QA_LEAN_WAUX 2   // cache policy of the weight requests: nt (streaming).  Against the default policy, alternating builds in one session
-                         // (profiles/r05_ab_lean_nt.txt): 1 x 4096 x 22016 10.2 -> 9.0 us in-kernel, x 12288 6.05 -> 5.63, 11008 x 4096 6.2 -> 5.8,
-                         // 16 x 4096 x 22016 15.6 -> 14.5; level at 4096 x 4096 -- the weights are read once and x stays in L2
-#endif
+constexpr int kLeanWAux = 2;     // cache policy of the weight requests: nt (streaming).  Against the default policy, alternating builds in one session
+                                 // (profiles/r05_ab_lean_nt.txt): 1 x 4096 x 22016 10.2 -> 9.0 us in-kernel, x 12288 6.05 -> 5.63, 11008 x 4096 6.2 -> 5.8,
+                                 // 16 x 4096 x 22016 15.6 -> 14.5; level at 4096 x 4096 -- the weights are read once and x stays in L2
 constexpr int kLeanStamps = 16;  // phase stamps per wave (tools builds): u64 s_memrealtime ticks
 
 // LDS of one lean workgroup (host and device agree through these functions)
@@ -53,25 +51,11 @@ struct LeanRest {
   float ln_eps;
   unsigned long long* span;
   unsigned long long* dbg;
-#ifdef QA_EXP_LEAN_OVERLAP   // (experiment builds only, DESIGN.md 9.2 / profiles/r06_launch_overlap.txt: a launch that starts BEFORE its predecessor has finished)
-  const unsigned* wait_sig;  // the predecessor's arrival word: this launch requests its weights at entry and asks for x only once the word says the predecessor's rows are in memory
-  unsigned* my_cnt;          // this launch's own exit counter (how many times it has run = which value of the arrival word to wait for)
-  unsigned wait_per_exec;    // arrivals the predecessor adds per run
-  unsigned my_per_exec;      // exits this launch adds per run
-  unsigned* signal;          // this launch's arrival word for ITS successor (every storing wave adds one behind its rows)
-#endif
 };
 
 // 64 lanes x 16 bytes: global (descriptor base + voff + soff) -> LDS (lds_addr + 16 * lane), exec-masked lanes write nothing.
 // s_nop 4: the operands may come straight from a v_readfirstlane (VALU writes SGPR -> VMEM reads it: 5 wait states).
-__device__ __forceinline__ void lean_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, unsigned lds_addr, bool coherent = false) {
-#ifdef QA_EXP_LEAN_OVERLAP
-  if (coherent) {
-    asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc0 sc1 lds" ::"s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-    return;
-  }
-#endif
-  (void)coherent;
+__device__ __forceinline__ void lean_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, unsigned lds_addr) {
   asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(voff), "s"(rsrc),
                "s"(soff)
                : "memory");
@@ -125,11 +109,7 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_lean_kernel(const half_t* __
   const unsigned pitch = (unsigned)aK * 2u + 16u;
   const int nseg = (T + 3) >> 2;
 
-#ifdef QA_EXP_LEAN_OVERLAP
-  const bool defer = rest.wait_sig != nullptr;
-#else
-  constexpr bool defer = false;
-#endif
+  // (a lambda, not straight-line code: folding it in changes hipcc's schedule of the lean kernels, and the encodings are pinned -- tools/kernel_table.py)
   const auto issue_x = [&]() __attribute__((always_inline)) {
   // ---- 1. x (and the norm weight) of this wave's K range: LDS-DMA, first in the memory queue ----
   {
@@ -140,14 +120,14 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_lean_kernel(const half_t* __
       const unsigned kbyte = (unsigned)(kb * 128 + 512 * s) * 2u;
       if (lane < 16 * (T - 4 * s)) {  // lanes past the wave's range write nothing (the neighbour wave owns those bytes)
         for (int tk = 0; tk < rows; ++tk)
-          lean_dma16(xr, (unsigned)lane * 16u, (unsigned)(row0 + tk) * (unsigned)aK * 2u + kbyte, lds_base + x_off + (unsigned)tk * pitch + kbyte, defer);
+          lean_dma16(xr, (unsigned)lane * 16u, (unsigned)(row0 + tk) * (unsigned)aK * 2u + kbyte, lds_base + x_off + (unsigned)tk * pitch + kbyte);
         if (ln) lean_dma16(lr, (unsigned)lane * 16u, kbyte, lds_base + lnw_off + kbyte);
       }
     }
   }
 
   };
-  if (!defer) issue_x();
+  issue_x();
   if constexpr (STAMP) ts[10] = __builtin_amdgcn_s_memrealtime();
 
   // ---- 2. the group words of four tiles per request (lane (n16, q): tile kb + 4 i + q -- with G = 128 one contiguous 256 bytes), then
@@ -175,26 +155,11 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_lean_kernel(const half_t* __
     for (int j = 0; j < TMAX; ++j)
 #pragma unroll
       for (int c = 0; c < NTW; ++c)
-        wq[c][j] = __builtin_amdgcn_raw_buffer_load_b128(wr, (unsigned)lane * 16u + (j < T ? 0u : 0x80000000u), ((unsigned)(blk * NTW + c) * (unsigned)KT + (unsigned)(kb + j)) * 1024u, QA_LEAN_WAUX);
+        wq[c][j] = __builtin_amdgcn_raw_buffer_load_b128(wr, (unsigned)lane * 16u + (j < T ? 0u : 0x80000000u), ((unsigned)(blk * NTW + c) * (unsigned)KT + (unsigned)(kb + j)) * 1024u, kLeanWAux);
     __builtin_amdgcn_sched_barrier(0);
   };
   request(nb);
   if constexpr (STAMP) ts[1] = __builtin_amdgcn_s_memrealtime();
-#ifdef QA_EXP_LEAN_OVERLAP
-  if (defer) {
-    // the weights are on their way; x is the predecessor's output: wait for its arrival word (bounded: a launch that cannot see it goes on and computes
-    // on whatever is there -- wrong numbers, never a hang), then make the rows visible (acquire at agent scope: the other XCDs' L2 lines of an x read
-    // in an earlier step are stale) and ask for x
-    const unsigned run = __hip_atomic_load(rest.my_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) / rest.my_per_exec;
-    const unsigned target = (run + 1u) * rest.wait_per_exec;
-    for (int spin = 0; spin < (1 << 16); ++spin) {
-      if ((int)(__hip_atomic_load(rest.wait_sig, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0) break;
-      __builtin_amdgcn_s_sleep(2);
-    }
-    issue_x();   // (sc1 requests: lean_dma16 below)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // x is the YOUNGEST request here: everything has landed
-  } else
-#endif
   // ---- 3. x has landed (it is older than every other request) ----
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LSET) : "memory");
   if constexpr (STAMP) ts[2] = __builtin_amdgcn_s_memrealtime();
@@ -406,11 +371,6 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_lean_kernel(const half_t* __
           if (4 * q + r < rows) {
             half_t hv = (half_t)(sum[r] + bv);
             if (rest.residual) hv = (half_t)((float)hv + (float)rest.residual[(size_t)m * aN + n]);   // to the ROUNDED product, as GEMM-then-add
-#ifdef QA_EXP_LEAN_OVERLAP
-            if (rest.signal != nullptr) {   // rows written THROUGH to memory (sc1): the successor on another XCD asks for them with sc1 loads, no cache-wide fence on either side
-              asm volatile("global_store_short %0, %1, off sc0 sc1" ::"v"(rest.Y + (size_t)m * aN + n), "v"((unsigned)__builtin_bit_cast(unsigned short, hv)) : "memory");
-            } else
-#endif
             rest.Y[(size_t)m * aN + n] = hv;
           }
         }
@@ -426,15 +386,6 @@ __global__ __launch_bounds__(WAVES * 64) void w4a16_lean_kernel(const half_t* __
   } else {
     compute_and_finish(szr, wq, nb, 0);
   }
-#ifdef QA_EXP_LEAN_OVERLAP
-  if (rest.signal != nullptr || rest.my_cnt != nullptr) {
-    if (wave < NTW) {   // (the waves that stored rows: one-block launches)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the written-through rows are acknowledged: in memory before the word
-      if (lane == 0 && rest.signal != nullptr) __hip_atomic_fetch_add(rest.signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (threadIdx.x == 0 && rest.my_cnt != nullptr) __hip_atomic_fetch_add(rest.my_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-#endif
   if constexpr (STAMP) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ts[9] = __builtin_amdgcn_s_memrealtime();

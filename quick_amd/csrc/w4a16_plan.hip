@@ -534,9 +534,7 @@ static int within_limits(const Req& r, const Pick& k) {
 // the CUs); bits 22-26: log2 of the poll limit in ticks of 10 ns (tests: 1 = every wave gives up at once).
 // (bits 4-7 = 8: the 256 x 256 tile -- waves of 256 tokens x 64 channels, a ring of two 64 KiB slots, one slice only)
 // AUTO's rule for the staggered two-slice launch: stages (128 k) per slice and output tiles
-#ifndef QA_XW_STAGGER_AUTO_D
-#define QA_XW_STAGGER_AUTO_D 1   // (A/B builds: -DQA_XW_STAGGER_AUTO_D=2 / 3)
-#endif
+constexpr int kXwStaggerAutoD = 1;   // (d = 2 / 3 were the A/B builds)
 static bool xw_stagger_auto(int stages_per_slice, int tiles) { return tiles == 128 && stages_per_slice >= 16; }
 static void shape_xw(const Req& r, const Pick& k, Plan& p) {
   const int M = r.M, N = r.N, KT = r.KT;
@@ -565,7 +563,7 @@ static void shape_xw(const Req& r, const Pick& k, Plan& p) {
   p.xw_stagger = 0;
   const auto stagger_fits = [&](int d) { return mb == 4 && pairs == 1 && s == 2 && r.G == 128 && KT % 2 == 0 && KT / 2 - d >= 4; };
   if (r.id.xw_stagger) p.xw_stagger = stagger_fits(r.id.xw_stagger) ? r.id.xw_stagger : 0;
-  else if (r.bare && xw_stagger_auto(KT / 2, p.ntiles) && stagger_fits(QA_XW_STAGGER_AUTO_D)) p.xw_stagger = QA_XW_STAGGER_AUTO_D;
+  else if (r.bare && xw_stagger_auto(KT / 2, p.ntiles) && stagger_fits(kXwStaggerAutoD)) p.xw_stagger = kXwStaggerAutoD;
   // XCDs per K slice: they form a gm x gn grid over the (token, channel) tiles; bytes per k and XCD: x rows (2 B) + weight columns (1/2 B)
   p.xcd_gm = xcd_rows(r, (long)p.ntiles * s, MBk, NBk, 8 / s, 64L * mb, 64L * pairs);
 }

@@ -689,7 +689,7 @@ def test_every_load_of_the_library_is_waited_for_before_its_registers_are_touche
 
 def test_no_vector_alu_instruction_hides_in_an_asm_statement_of_hipcc_scheduled_code():
     """[r06] The source-level half of the above: in the hipcc-scheduled translation units (everything but the generated loops, which are whole
-    K loops with their own asserted distances) no asm statement of the default build contains a VALU instruction that computes -- and_or() is
+    K loops with their own asserted distances) no asm statement contains a VALU instruction that computes -- and_or() is
     `(a & m) | o` on operands made opaque by EMPTY asm statements, so that v_and_or_b32 is hipcc's own instruction.  Allowed: the exchange-K
     queue's v_accvgpr_read_b32 (covered by the ISA lint), memory / scalar / wait instructions."""
     import re
@@ -699,7 +699,6 @@ def test_no_vector_alu_instruction_hides_in_an_asm_statement_of_hipcc_scheduled_
         if fn.endswith("_loop.inc") or not fn.endswith((".hpp", ".hip", ".cpp")):
             continue
         text = open(os.path.join(root, fn)).read()
-        text = re.sub(r"#if defined\(QA_ANDOR_ASM\).*?#else", "", text, flags=re.S)          # (the A/B arms of and_or)
         for m in re.finditer(r"asm\s*(?:volatile)?\s*\(\s*((?:\"(?:[^\"\\\\]|\\\\.)*\"\s*)+)", text):
             body = "".join(re.findall(r"\"((?:[^\"\\\\]|\\\\.)*)\"", m.group(1)))
             for ins in re.split(r"\\n\\t|\\n|;", body):
@@ -707,6 +706,33 @@ def test_no_vector_alu_instruction_hides_in_an_asm_statement_of_hipcc_scheduled_
                 if mn.startswith("v_") and not mn.startswith(("v_accvgpr_read", "v_readfirstlane", "v_readlane")):
                     offenders.append((fn, ins.strip()[:60]))
     assert not offenders, offenders[:5]
+
+
+def test_product_sources_have_no_compile_time_switch_but_the_tools_one():
+    """A/B experiments live as patches under tools/patches/ (tools/build_variant.sh applies them to a copy), not as switches in the product's
+    sources: every preprocessor conditional under quick_amd/csrc/ names QUICK_AMD_TOOLS and nothing else (the sources use #pragma once: no
+    include guards), and the build defines no other macro."""
+    import re
+    from quick_amd import build
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "quick_amd", "csrc")
+    seen, offenders = 0, []
+    for fn in sorted(os.listdir(root)):
+        if not fn.endswith((".hip", ".hpp", ".cpp", ".inc")):
+            continue
+        for no, line in enumerate(open(os.path.join(root, fn)), 1):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if m is None:
+                continue
+            seen += 1
+            cond = re.sub(r"//.*|/\*.*?\*/", "", m.group(2))
+            names = set(re.findall(r"[A-Za-z_]\w*", cond)) - {"defined"}
+            if names != {"QUICK_AMD_TOOLS"}:
+                offenders.append((fn, no, line.strip()[:80]))
+    assert seen > 0 and not offenders, offenders[:5]
+    flags = list(build.CFLAGS) + [f for extra in build.EXTRA_CFLAGS.values() for f in extra]
+    assert [f for f in flags if f.startswith("-D") and f != "-DQUICK_AMD_TOOLS"] == []
+    src = open(build.__file__).read()
+    assert set(re.findall(r"-D\w*", src)) == {"-DQUICK_AMD_TOOLS"}, "quick_amd/build.py passes a -D other than -DQUICK_AMD_TOOLS"
 
 
 def test_generated_k_loops_are_what_the_generator_writes(tmp_path):
@@ -731,7 +757,7 @@ def test_generated_mid_token_loops_are_what_the_generator_writes(tmp_path, monke
     (no vmcnt(0) drain inside a loop copy except where the walk says nothing is behind the piece), and the six tile shapes exist."""
     import importlib.util
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for k in ("XM_EXP", "XM_OUT", "XM_D", "XM_RS", "XM_TOUCH", "XM_BARRIER", "XM_WFIRST", "XM_W_NT", "XM_JITQ", "XM_SBAR", "XM_BURST"):
+    for k in ("XM_EXP", "XM_OUT", "XM_D", "XM_TOUCH", "XM_BARRIER", "XM_WFIRST", "XM_W_NT", "XM_JITQ", "XM_SBAR"):
         monkeypatch.delenv(k, raising=False)
     monkeypatch.syspath_prepend(os.path.join(root, "tools"))
     spec = importlib.util.spec_from_file_location("gen_xm_loop", os.path.join(root, "tools", "gen_xm_loop.py"))

@@ -65,7 +65,6 @@ X_POLICY = (" " + os.environ["XM_X_POLICY"].strip()) if os.environ.get("XM_X_POL
 JITQ_ENV = os.environ.get("XM_JITQ", "")                # "q": every configuration requests W(s + 1) in quarter q of stage s; "-1": none does (A/B switch; default: Cfg.jitq)
 SBAR = os.environ.get("XM_SBAR", "")                   # quarters at whose head every stage has a workgroup barrier (e.g. "0" or "1,3"): phase-locks the waves' requests (A/B switch;
                                                        # only for shapes whose waves own equally many k tiles)
-BURST = os.environ.get("XM_BURST", "0") != "0"         # x pieces of a half in one burst at the head of its quarter instead of one every few MFMAs (A/B switch)
 EXP = int(os.environ.get("XM_EXP", "0"))   # timing experiments (wrong results; never checked in): 1 no MFMAs, 2 no vector memory, 4 no dequantisation,
                                             # 8 no fragment reads, 16 no weight loads, 32 no x pieces (16 / 32: and no counted waits)
 
@@ -81,7 +80,7 @@ def need(tag):
 
 
 class Cfg:
-    def __init__(self, MB, PR, D, VBASE=24, RS=1, jitq=-1):
+    def __init__(self, MB, PR, D, VBASE=24, jitq=-1):
         # jitq >= 0: W(s + 1) leaves in quarter jitq of stage s, right behind that quarter's x pieces, into a queue of two slots -- instead of
         # W(s + D) at the end of stage s.  A wave's loads return in issue order, so an x piece waits for every weight request in front of it:
         # weights requested D stages ahead hold back x that is needed half a stage ahead.  Measured (profiles/r06_xm_anatomy.txt): 3-9 % off the
@@ -90,12 +89,12 @@ class Cfg:
             jitq = int(JITQ_ENV)
         if jitq >= 0 and not DQ:
             D = 2
-        assert MB in (1, 2) and PR in (1, 2, 3) and D >= 2 and RS in (1, 2) and D % RS == 0
-        self.MB, self.PR, self.D, self.VBASE, self.RS, self.jitq = MB, PR, D, VBASE, RS, jitq   # RS: stages of the wave's x ring
+        assert MB in (1, 2) and PR in (1, 2, 3) and D >= 2
+        self.MB, self.PR, self.D, self.VBASE, self.jitq = MB, PR, D, VBASE, jitq
         self.NX = 4 * MB                    # LDS-DMA instructions per half stage (8 rows x 128 B each)
         self.LW = 3 * PR                    # weight-side loads per stage
         self.HB = MB * 4096                 # bytes of a half-stage slot
-        self.RING = 2 * self.HB * RS        # the wave's ring: RS stages
+        self.RING = 2 * self.HB             # the wave's ring: one stage
         self.NACC = PR * MB
         self.QS = even(9 * PR)              # queue slot: per pair lo[4] hi[4], then sz per pair
         self.AXF = 128 - 2 * MB * 2 * 4     # x fragments [buf][blk][uu][4] live in the LAST accumulator registers (ds_read writes, MFMA reads them)
@@ -157,29 +156,29 @@ class Cfg:
     def weight_dword(self, d, p, u):
         return self.Q(d, "lo" if u % 2 == 0 else "hi", p, u >> 1)
 
-    def x_reads(self, q, buf, rs=0):
-        """the B fragments of quarter q (k16 steps 2 q, 2 q + 1 of the stage in ring slot rs: half q / 2 of it) into buffer buf: MB x 2 ds_read_b128"""
+    def x_reads(self, q, buf):
+        """the B fragments of quarter q (k16 steps 2 q, 2 q + 1 of the stage in the ring: half q / 2 of it) into buffer buf: MB x 2 ds_read_b128"""
         out = []
         for blk in range(self.MB):
             for uu in range(2):
                 r = self.XF(buf, blk, uu)
                 ra = self.VRA + (q % 2) * 2 + uu
-                out.append(I(f"ds_read_b128 {a(r, 4)}, {v(ra)} offset:{rs * 2 * self.HB + (q // 2) * self.HB + blk * 4096}", "lds", [("a", x) for x in range(r, r + 4)], [ra]))
+                out.append(I(f"ds_read_b128 {a(r, 4)}, {v(ra)} offset:{(q // 2) * self.HB + blk * 4096}", "lds", [("a", x) for x in range(r, r + 4)], [ra]))
         return out
 
-    def x_dma(self, h, tag=None, rs=0):
+    def x_dma(self, h, tag=None):
         """the pieces of half h of the stage whose row offsets are in S_XQ (descriptor S_DX: live or dead) into slot h, as (M0 write, LDS-DMA)
         pairs; the caller puts at least one instruction between the two"""
         out = []
         for i in range(self.NX):
             ld = I(f"buffer_load_dwordx4 {v(self.VX + i)}, {sr(S_DX, 4)}, {s(S_XQ[h])} offen{X_POLICY} lds", "vmem", [], ["m0"])
             ld.tag = tag
-            out.append((I(f"s_add_u32 m0, {XDST}, {rs * 2 * self.HB + h * self.HB + i * 1024}", "salu", ["m0"], []), ld))
+            out.append((I(f"s_add_u32 m0, {XDST}, {h * self.HB + i * 1024}", "salu", ["m0"], []), ld))
         return out
 
-    def x_dma_flat(self, h, tag=None, rs=0):
+    def x_dma_flat(self, h, tag=None):
         out = []
-        for m, ld in self.x_dma(h, tag, rs):
+        for m, ld in self.x_dma(h, tag):
             out += [m, I("s_nop 0", "salu"), ld]
         return out
 
@@ -238,8 +237,7 @@ class Cfg:
         for i in range(5):
             for c in per:
                 out.append(c[i])
-        RS, rs = self.RS, sa % self.RS
-        out += self.x_offsets(RS, (0, 1))
+        out += self.x_offsets(1, (0, 1))
         chains = []
         for u in range(8):
             for p in range(PR):
@@ -256,14 +254,10 @@ class Cfg:
                 # head of quarter q: the next quarter's fragments (of this stage, or quarter 0 of the next); in quarters 1 and 3 the half whose
                 # last fragments were read a quarter ago is refilled with the pieces of stage sa + 1, one LDS-DMA every few MFMAs
                 out.append(need(("x", sa, (q + 1) // 2) if q < 3 else ("x", sa + 1, 0)))
-                out += self.x_reads((q + 1) % 4, (q + 1) % 2, rs if q < 3 else (rs + 1) % RS)
-                pend = self.x_dma(q // 2, ("x", sa + RS, q // 2), rs) if q % 2 == 1 else []
+                out += self.x_reads((q + 1) % 4, (q + 1) % 2)
+                pend = self.x_dma(q // 2, ("x", sa + 1, q // 2)) if q % 2 == 1 else []
                 if SBAR and str(q) in SBAR.split(","):
                     out.append(I("s_barrier", "wait"))
-                if BURST and pend:
-                    for m0w, ld in pend:
-                        out += [m0w, I("s_nop 0", "salu"), ld]
-                    pend = []
                 if q == self.jitq:
                     out += self.w_offsets(1)
                     pend += [(I("s_nop 0", "salu"), ld) for ld in self.w_loads((d + 1) % self.D, ("w", sa + 1))]
@@ -326,11 +320,9 @@ class Cfg:
                     I(f"v_mad_u32_u24 {v(self.VX + i)}, {v(tmp)}, %[k2], %[xc{i % 2}]", "valu", [self.VX + i], [tmp])]
         # x of stage 0 first (it comes from L2, and everything behind it in the queue waits for it anyway), then W(0) .. W(D - 1); the first
         # fragments as soon as x(0, 0) is there, then -- slot 0 free -- the first pieces of stage 1
-        xs = []
-        for r in range(self.RS):
-            xs += self.x_offsets(r, (0, 1))
-            for h in range(2):
-                xs += self.x_dma_flat(h, ("x", r, h), r)
+        xs = self.x_offsets(0, (0, 1))
+        for h in range(2):
+            xs += self.x_dma_flat(h, ("x", 0, h))
         w0 = self.w_offsets(0) + self.w_loads(0, ("w", 0))
         # W(0) FIRST: its trip to HBM is the longest wait of the launch and everything queued behind it comes back behind it anyway
         pro += (w0 + xs) if WFIRST else xs
@@ -461,11 +453,9 @@ def run_macro(c):
     return body
 
 
-_RS = int(os.environ.get("XM_RS", "1"))   # ring stages of the 32-token configurations (A/B switch; two measured level with one: the second stage's pieces
-                                          # sit in front of the weights in the in-order queue and the first tile starts later by what the loop gains)
 _D = [int(x) for x in DQ.split(",")] if DQ else [4, 4, 2, 4, 4, 2]
-CONFIGS = [Cfg(2, 1, _D[0]), Cfg(2, 2, _D[1], jitq=1), Cfg(2, 3, _D[2], VBASE=16, jitq=1), Cfg(1, 1, _D[3], RS=_RS), Cfg(1, 2, _D[4], RS=_RS, jitq=1),
-           Cfg(1, 3, _D[5], VBASE=16, RS=_RS, jitq=1)]
+CONFIGS = [Cfg(2, 1, _D[0]), Cfg(2, 2, _D[1], jitq=1), Cfg(2, 3, _D[2], VBASE=16, jitq=1), Cfg(1, 1, _D[3]), Cfg(1, 2, _D[4], jitq=1),
+           Cfg(1, 3, _D[5], VBASE=16, jitq=1)]
 
 
 def generate():
@@ -480,8 +470,8 @@ def generate():
         body += "#ifdef QUICK_AMD_TOOLS\n#define QA_XM_ASM_STAMPED_%s \\\n" % c.name
         body += "".join(l + " \\\n" for l in stext.rstrip("\n").split("\n")) + "\n#endif\n"
         body += run_macro(c)
-        info.append("config (%d, %d): %d instructions, VGPRs v%d..v%d, queue of %d stages, ring %d KiB per wave (%d stages); vmcnt prologue %s first %s loop %s"
-                    % (c.MB, c.PR, n, c.VBASE, c.VEND - 1, c.D, c.RING // 1024, c.RS, counts[0], counts[1], [counts[2][d] for d in range(c.D)]))
+        info.append("config (%d, %d): %d instructions, VGPRs v%d..v%d, queue of %d stages, ring %d KiB per wave; vmcnt prologue %s first %s loop %s"
+                    % (c.MB, c.PR, n, c.VBASE, c.VEND - 1, c.D, c.RING // 1024, counts[0], counts[1], [counts[2][d] for d in range(c.D)]))
     return body, info
 
 

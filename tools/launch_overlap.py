@@ -1,5 +1,5 @@
 """Experiment: overlap the fixed cost of DEPENDENT small-M launches.  The weights of launch i + 1 do not depend on launch i --
-only x does.  An experiment build of the lean kernels (tools/build_variant.sh ... -DQA_EXP_LEAN_OVERLAP) lets a launch start without waiting for its
+only x does.  An experiment build of the lean kernels (tools/patches/lean_launch_overlap.patch as the patch argument of tools/build_variant.sh: tools/patches/README.md) lets a launch start without waiting for its
 predecessor: it requests its weight tiles at entry, polls an arrival word the predecessor's storing waves raise behind their rows, then asks for x.
 Here: the o_proj -> gate_up pair of a Llama-2-7B layer at one token (4096 x 4096 with the residual, then 4096 x 22016 with the RMSNorm prologue and
 SiLU * mul), R pairs in one hipGraph, HBM-cold weight sets; `chain` = ordinary edges on one stream, `overlap` = every gate_up on a second stream forked
@@ -10,7 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from quick_amd import _lib, packing, kernels
 lib = _lib.load()
-assert hasattr(lib, "quick_amd_exp_lean_overlap"), "needs the -DQA_EXP_LEAN_OVERLAP build (QUICK_AMD_LIB_OVERRIDE)"
+assert hasattr(lib, "quick_amd_exp_lean_overlap"), "needs the build of tools/patches/lean_launch_overlap.patch (QUICK_AMD_LIB_OVERRIDE)"
 lib.quick_amd_exp_lean_overlap.restype = None
 lib.quick_amd_exp_lean_overlap.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
 dev = torch.device("cuda:0")

@@ -1,5 +1,6 @@
 """Diagnostic: the four-tile fragment flavour of the skinny kernel against the oracle, per 16-channel tile, under whatever library
-QUICK_AMD_LIB_OVERRIDE names (tools/bin/ab_uncond*.so: the chunk loop with unconditional requests).    python tools/skinny_uncond_check.py [reps]"""
+QUICK_AMD_LIB_OVERRIDE names (tools/bin/ab_uncond*.so: the chunk loop with unconditional requests, tools/patches/skinny_uncond_requests.patch as the patch
+argument of tools/build_variant.sh -- tools/patches/README.md).    python tools/skinny_uncond_check.py [reps]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

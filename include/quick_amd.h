@@ -299,6 +299,29 @@ int quick_padded_in_features(int K, int group_size);
 int quick_repack_cuda_to_mi355x_padded(const void* qweight_in, const void* scales_in, const void* qzeros_in, void* qweight_out,
                                        void* scales_out, void* qzeros_out, int K, int N, int group_size, void* hip_stream);
 
+/*
+ * GEMM-format bridge: AWQ checkpoints in the packing of WQLinear_GEMM (quick/awq/modules/linear/gemm.py:29-63, 108-143) <-> mi355x
+ * order.  Both hold the same (iw[K, N], z[K/G, N], s[K/G, N]); the conversion is a permutation of bits, lossless in both directions.
+ * The GEMM packing in closed form, order = {0, 2, 4, 6, 1, 3, 5, 7}:
+ *   qweight  int32 [K, N/8]     nibble i of dword c of row k = iw[k, 8c + order[i]]
+ *   qzeros   int32 [K/G, N/8]   nibble i of dword c of row g = z[g, 8c + order[i]]
+ *   scales   fp16  [K/G, N]     plain, not duplicated
+ * quick_repack_awq_gemm_to_mi355x always writes Kp = quick_padded_in_features(K, G) rows (Kp == K when K % 128 == 0): outputs are
+ * qweight [Kp/4, N/2], scales [Kp/G, 2N], qzeros [Kp/G, N/4]; rows at or beyond K hold weight 0, groups at or beyond K/G scale 0 and
+ * zero point 0.  quick_repack_mi355x_to_awq_gemm is the inverse for K % 128 == 0 (a padded copy is never turned back); it reads the
+ * zero points from the scale words (qzeros_in is not read).  Inputs and outputs must not alias.
+ * Answered before any GPU work, with a sentence in quick_amd_last_error():
+ *   K, N or G <= 0, N % 8 != 0, G % 32 != 0, K % G != 0, K % 32 != 0, a null pointer   QUICK_ERR_INVALID_ARGUMENT
+ *   N % 128 != 0 (the GEMM kernels' envelope)                                            QUICK_ERR_UNSUPPORTED
+ *   K % 128 != 0, mi355x -> GEMM packing only                                            QUICK_ERR_UNSUPPORTED
+ */
+int quick_repack_awq_gemm_to_mi355x(const void* qweight_in, const void* qzeros_in, const void* scales_in,
+                                    void* qweight_out, void* scales_out, void* qzeros_out,
+                                    int K, int N, int group_size, void* hip_stream);
+int quick_repack_mi355x_to_awq_gemm(const void* qweight_in, const void* scales_in, const void* qzeros_in,
+                                    void* qweight_out, void* qzeros_out, void* scales_out,
+                                    int K, int N, int group_size, void* hip_stream);
+
 /* Dequantise an MI355X-order layer to a dense fp16 [K, N] row-major matrix (debug / parity aid;
  * counterpart of the reference CPU path quick/awq/utils/packing_utils.py:82-97). */
 int quick_dequantize_mi355x_f16(const void* qweight, const void* scales, const void* qzeros,

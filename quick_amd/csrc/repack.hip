@@ -6,6 +6,8 @@
 #include "w4a16_common.hpp"
 #include "../../include/quick_amd.h"
 
+#include <cstdio>
+
 namespace quick_amd {
 
 // dword index + nibble of logical weight (k, n) in the reference layout (closed form)
@@ -107,6 +109,128 @@ __global__ __launch_bounds__(256) void repack_sz_mi355x_to_cuda(const uint32_t* 
   atomicOr(z_out + (size_t)g * (N >> 2) + (x >> 2), (z << (4 * (x & 3))) | (z << (4 * (x & 3) + 16)));
 }
 
+// ------------------------------------------------------------------------------------------------
+// AWQ "GEMM packing" (WQLinear_GEMM checkpoints) <-> mi355x order.  GEMM packing, closed form: qweight int32 [K, N/8], nibble i of
+// dword c of row k = iw[k, 8c + order[i]], order = {0, 2, 4, 6, 1, 3, 5, 7}; qzeros int32 [K/G, N/8], the same packing of z[g, n];
+// scales fp16 [K/G, N] plain.  Channel 8c + m therefore sits at nibble awq_nibble(m) = {0, 4, 1, 5, 2, 6, 3, 7}[m] = (m >> 1) + 4 * (m & 1).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int awq_nibble(int m) { return (m >> 1) + 4 * (m & 1); }
+__device__ __forceinline__ int awq_channel(int i) { return 2 * (i & 3) + (i >> 2); }   // order[i]
+
+constexpr int kAwqTileK = 128;    // rows of a staged block = one k tile of the mi355x order
+constexpr int kAwqTileN = 256;    // channels of a staged block (the last block of a row of blocks holds 128 when N % 256 == 128)
+constexpr int kAwqRowPad = 1;     // LDS row stride 33 / 17 dwords: the rows k0 + j, k0 + 8 + j, ... a wave gathers from fall on distinct banks
+
+// Weights: every mi355x dword is an 8 x 8 nibble transpose of eight GEMM-packing dwords from eight consecutive rows.  A workgroup stages
+// 128 k x 256 (128) channels through LDS -- each input dword read once, in 16-byte pieces of whole 128- (64-) byte row segments -- and
+// writes the 16 (8) output tiles of 1 KiB as one 16-byte piece per lane.  Grid: (ceil(N / 256), Kp / 128); rows >= K_in are padding (0).
+__global__ __launch_bounds__(256) void repack_weight_awq_gemm_to_mi355x(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                                         int Kp, int N, int K_in) {
+  __shared__ uint32_t tile[kAwqTileK * (kAwqTileN / 8 + kAwqRowPad)];
+  const int n0 = blockIdx.x * kAwqTileN, kt = blockIdx.y;
+  const int nc = min(kAwqTileN, N - n0);          // 256 or 128
+  const int W = nc >> 3, W4 = nc >> 5;            // dwords / 16-byte pieces per staged row
+  const int stride = W + kAwqRowPad;
+  const size_t ND = (size_t)(N >> 3);             // dwords per input row
+  for (int p = threadIdx.x; p < kAwqTileK * W4; p += 256) {
+    const int r = p / W4, c4 = p % W4;
+    const int k = kt * kAwqTileK + r;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (k < K_in) v = *(const u32x4*)(in + (size_t)k * ND + (size_t)(n0 >> 3) + 4 * c4);
+    uint32_t* dst = tile + r * stride + 4 * c4;
+    dst[0] = v[0]; dst[1] = v[1]; dst[2] = v[2]; dst[3] = v[3];
+  }
+  __syncthreads();
+  const int KT = Kp >> 7;
+  for (int p = threadIdx.x; p < (nc >> 4) * 64; p += 256) {     // one 16-byte piece of an output tile: lane `lane` of tile (n / 16, kt)
+    const int ntl = p >> 6, lane = p & 63;
+    const int nl = ntl * 16 + (lane & 15);
+    const int col = nl >> 3, sh = 4 * awq_nibble(nl & 7);
+    u32x4 o;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t* src = tile + (t * 32 + 8 * (lane >> 4)) * stride + col;
+      uint32_t v = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v |= ((src[j * stride] >> sh) & 15u) << (4 * (4 * (j & 1) + (j >> 1)));
+      o[t] = v;
+    }
+    const size_t tileidx = (size_t)((n0 >> 4) + ntl) * KT + kt;
+    *(u32x4*)(out + (tileidx * 64 + lane) * 4) = o;
+  }
+}
+
+// scales / zeros, GEMM packing -> mi355x order: one thread per (g, n) writes the (scale | zero point << 16) word; groups >= NG_in are padding
+__global__ __launch_bounds__(256) void repack_sz_awq_gemm_to_mi355x(const half_t* __restrict__ s_in, const uint32_t* __restrict__ z_in,
+                                                                     uint32_t* __restrict__ sz_out, int NG, int N, int NG_in) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)NG * N) return;
+  const int g = (int)(i / N), n = (int)(i % N);
+  uint32_t w = 0u;
+  if (g < NG_in) {
+    const uint32_t z = (z_in[(size_t)g * (N >> 3) + (n >> 3)] >> (4 * awq_nibble(n & 7))) & 15u;
+    w = (uint32_t)__builtin_bit_cast(unsigned short, s_in[(size_t)g * N + n]) | (z << 16);
+  }
+  sz_out[group_word_index(g, n, NG)] = w;
+}
+
+// the plain copy of the zero points (nibble n % 8 of dword n / 8 of a row of N / 4 dwords, whose second half stays 0): one thread per output
+// dword puts the eight nibbles of the same input dword in channel order, or writes the 0
+__global__ __launch_bounds__(256) void repack_z_awq_gemm_to_mi355x(const uint32_t* __restrict__ z_in, uint32_t* __restrict__ z_out,
+                                                                    int NG, int N, int NG_in) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t ND = (size_t)(N >> 3), row = (size_t)(N >> 2);
+  if (i >= (size_t)NG * row) return;
+  const size_t g = i / row, c = i % row;
+  uint32_t v = 0u;
+  if (g < (size_t)NG_in && c < ND) {
+    const uint32_t q = z_in[g * ND + c];
+#pragma unroll
+    for (int m = 0; m < 8; ++m) v |= ((q >> (4 * awq_nibble(m))) & 15u) << (4 * m);
+  }
+  z_out[i] = v;
+}
+
+// mi355x order -> GEMM packing (state_dict(), saving): gathers, one thread per output dword.  K % 128 == 0.
+__global__ __launch_bounds__(256) void repack_weight_mi355x_to_awq_gemm(const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                                         int K, int N) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t ND = (size_t)(N >> 3);
+  if (i >= (size_t)K * ND) return;
+  const int k = (int)(i / ND), c = (int)(i % ND);
+  const int KT = K >> 7, j = k & 7;
+  const int sh = 4 * (4 * (j & 1) + (j >> 1));
+  uint32_t v = 0u;
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const int n = 8 * c + awq_channel(b);
+    const int lane = (n & 15) + 16 * ((k & 31) >> 3);
+    const size_t d = (((size_t)(n >> 4) * KT + (k >> 7)) * 64 + lane) * 4 + ((k & 127) >> 5);
+    v |= ((in[d] >> sh) & 15u) << (4 * b);
+  }
+  out[i] = v;
+}
+
+// one thread per (g, n / 8): eight scale words -> eight fp16 scales (one 16-byte store) and one dword of zero points (read from the words)
+__global__ __launch_bounds__(256) void repack_sz_mi355x_to_awq_gemm(const uint32_t* __restrict__ sz_in, half_t* __restrict__ s_out,
+                                                                     uint32_t* __restrict__ z_out, int NG, int N) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t ND = (size_t)(N >> 3);
+  if (i >= (size_t)NG * ND) return;
+  const int g = (int)(i / ND), c = (int)(i % ND);
+  const uint32_t* w = sz_in + group_word_index(g, 8 * c, NG);    // 8c .. 8c + 7 lie in one 16-channel block: consecutive words
+  uint32_t z = 0u;
+  u32x4 s;
+#pragma unroll
+  for (int m = 0; m < 8; m += 2) {
+    const uint32_t a = w[m], b = w[m + 1];
+    s[m >> 1] = (a & 0xffffu) | (b << 16);
+    z |= (((a >> 16) & 15u) << (4 * awq_nibble(m))) | (((b >> 16) & 15u) << (4 * awq_nibble(m + 1)));
+  }
+  *(u32x4*)(s_out + (size_t)g * N + 8 * (size_t)c) = s;
+  z_out[i] = z;
+}
+
 static int check(int K, int N, int G) {
   if (K <= 0 || N <= 0 || G <= 0 || N % 128 != 0 || G % 32 != 0 || K % G != 0) return QUICK_ERR_INVALID_ARGUMENT;
   if (K % 128 != 0) return QUICK_ERR_UNSUPPORTED;
@@ -170,6 +294,58 @@ int quick_repack_mi355x_to_cuda(const void* qweight_in, const void* scales_in, c
   hipLaunchKernelGGL(repack_sz_mi355x_to_cuda, dim3((unsigned)(((size_t)NG * N + 255) / 256)), dim3(256), 0, st,
                      (const uint32_t*)scales_in, (half_t*)scales_out, (uint32_t*)qzeros_out, NG, N);
   return hipGetLastError() == hipSuccess ? QUICK_OK : QUICK_ERR_LAUNCH;
+}
+
+// shape rules of the GEMM-packing bridge, answered before any GPU work (include/quick_amd.h)
+static int check_awq_gemm(const char* fn, int K, int N, int G, bool need_k128) {
+  char text[256];
+  const char* why = nullptr;
+  int code = QUICK_ERR_INVALID_ARGUMENT;
+  if (K <= 0 || N <= 0 || G <= 0) why = "non-positive dimension";
+  else if (N % 8 != 0) why = "OC is not multiple of pack_num = 8";
+  else if (G % 32 != 0) why = "Group size should be a multiple of 32";
+  else if (K % G != 0) why = "in_features is not a multiple of the group size";
+  else if (K % 32 != 0) why = "in_features must be a multiple of 32";
+  else {
+    code = QUICK_ERR_UNSUPPORTED;
+    if (N % 128 != 0) why = "OC must be a multiple of 128 for the MI355X GEMM kernels";
+    else if (need_k128 && K % 128 != 0) why = "in_features must be a multiple of 128: a padded MI355X copy is never turned back";
+  }
+  if (!why) return QUICK_OK;
+  snprintf(text, sizeof(text), "%s: %s (K=%d N=%d G=%d)", fn, why, K, N, G);
+  return set_last_error(code, text);
+}
+
+int quick_repack_awq_gemm_to_mi355x(const void* qweight_in, const void* qzeros_in, const void* scales_in, void* qweight_out,
+                                    void* scales_out, void* qzeros_out, int K, int N, int group_size, void* hip_stream) {
+  if (int rc = check_awq_gemm("quick_repack_awq_gemm_to_mi355x", K, N, group_size, false)) return rc;
+  if (!qweight_in || !qzeros_in || !scales_in || !qweight_out || !scales_out || !qzeros_out)
+    return set_last_error(QUICK_ERR_INVALID_ARGUMENT, "quick_repack_awq_gemm_to_mi355x: null tensor pointer");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int Kp = quick_padded_in_features(K, group_size);
+  const int NG = Kp / group_size, NG_in = K / group_size;
+  hipLaunchKernelGGL(repack_weight_awq_gemm_to_mi355x, dim3((unsigned)((N + kAwqTileN - 1) / kAwqTileN), (unsigned)(Kp / kAwqTileK)),
+                     dim3(256), 0, st, (const uint32_t*)qweight_in, (uint32_t*)qweight_out, Kp, N, K);
+  hipLaunchKernelGGL(repack_sz_awq_gemm_to_mi355x, dim3((unsigned)(((size_t)NG * N + 255) / 256)), dim3(256), 0, st,
+                     (const half_t*)scales_in, (const uint32_t*)qzeros_in, (uint32_t*)scales_out, NG, N, NG_in);
+  hipLaunchKernelGGL(repack_z_awq_gemm_to_mi355x, dim3((unsigned)(((size_t)NG * (N / 4) + 255) / 256)), dim3(256), 0, st,
+                     (const uint32_t*)qzeros_in, (uint32_t*)qzeros_out, NG, N, NG_in);
+  return hipGetLastError() == hipSuccess ? QUICK_OK : set_last_error(QUICK_ERR_LAUNCH, "quick_repack_awq_gemm_to_mi355x: launch failed");
+}
+
+int quick_repack_mi355x_to_awq_gemm(const void* qweight_in, const void* scales_in, const void* qzeros_in, void* qweight_out,
+                                    void* qzeros_out, void* scales_out, int K, int N, int group_size, void* hip_stream) {
+  if (int rc = check_awq_gemm("quick_repack_mi355x_to_awq_gemm", K, N, group_size, true)) return rc;
+  if (!qweight_in || !scales_in || !qweight_out || !qzeros_out || !scales_out)
+    return set_last_error(QUICK_ERR_INVALID_ARGUMENT, "quick_repack_mi355x_to_awq_gemm: null tensor pointer");
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int NG = K / group_size;
+  (void)qzeros_in;  // the zero points travel in the scales tensor's words
+  hipLaunchKernelGGL(repack_weight_mi355x_to_awq_gemm, dim3((unsigned)(((size_t)K * (N / 8) + 255) / 256)), dim3(256), 0, st,
+                     (const uint32_t*)qweight_in, (uint32_t*)qweight_out, K, N);
+  hipLaunchKernelGGL(repack_sz_mi355x_to_awq_gemm, dim3((unsigned)(((size_t)NG * (N / 8) + 255) / 256)), dim3(256), 0, st,
+                     (const uint32_t*)scales_in, (half_t*)scales_out, (uint32_t*)qzeros_out, NG, N);
+  return hipGetLastError() == hipSuccess ? QUICK_OK : set_last_error(QUICK_ERR_LAUNCH, "quick_repack_mi355x_to_awq_gemm: launch failed");
 }
 
 }  // extern "C"

@@ -19,6 +19,8 @@ inline bool lds_limit_once(std::atomic<unsigned long long>& done, const void* kf
   done.fetch_or(bit, std::memory_order_release);
   return true;
 }
+// Leave `text` in quick_amd_last_error() for the calling thread and return `code` (defined next to the buffer, w4a16_gemm.hip).
+int set_last_error(int code, const char* text);
 }  // namespace quick_amd
 
 namespace quick_amd {

@@ -71,6 +71,9 @@ static int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+// (the other translation units of the library leave their sentence through this one: w4a16_common.hpp)
+int quick_amd::set_last_error(int code, const char* text) { return fail(code, "%s", text); }
+
 static int check_shapes(int M, int K, int N, int G) {
   if (M <= 0 || K <= 0 || N <= 0 || G <= 0) return fail(QUICK_ERR_INVALID_ARGUMENT, "non-positive dimension");
   // same messages as csrc/gemm_cuda_quick.cu:1479-1484

@@ -11,6 +11,7 @@ from typing import Optional, Tuple
 import torch
 
 from .linear import WQLinear_QUICK
+from .linear_gemm import WQLinear_GEMM
 
 
 def QUICK_cat(*input_layers: torch.Tensor, options: str, reshape_dims: Optional[Tuple[int, int]] = None) -> torch.Tensor:
@@ -55,4 +56,17 @@ def fuse_qkv_quick(module, q_proj, k_proj, v_proj):
         QUICK_cat(*[p[2] for p in packed], options="qzeros").to(dev),
         prepared=False)
     qkv_layer.bias = torch.cat([q_proj.bias, k_proj.bias, v_proj.bias], dim=0) if q_proj.bias is not None else None
+    return qkv_layer
+
+
+def fuse_qkv_gemm(module, q_proj, k_proj, v_proj):
+    """One WQLinear_GEMM computing [q | k | v]: the GEMM packing concatenates along dim 1 (eight channels per dword, every width a
+    multiple of 8), so unequal widths are fine.  Works on ``state_dict``-order tensors, whatever the three modules hold now."""
+    dev = q_proj.qweight.device if module is None else next(iter(module.state_dict().values())).device
+    qkv_layer = WQLinear_GEMM(
+        q_proj.w_bit, q_proj.group_size, q_proj.in_features,
+        q_proj.out_features + k_proj.out_features + v_proj.out_features, q_proj.bias is not None, dev)
+    packed = [p.awq_gemm_order() for p in (q_proj, k_proj, v_proj)]
+    qkv_layer._set_packed(*[torch.cat([p[i] for p in packed], dim=1).to(dev) for i in range(3)], prepared=False)
+    qkv_layer.bias = torch.cat([q_proj.bias, k_proj.bias, v_proj.bias], dim=0).to(dev) if q_proj.bias is not None else None
     return qkv_layer

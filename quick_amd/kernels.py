@@ -313,6 +313,65 @@ def repack_mi355x_to_cuda(qweight, scales, qzeros):
     return _repack("quick_repack_mi355x_to_cuda", qweight, scales, qzeros)
 
 
+def _awq_gemm_dims(rows, n8, groups, what):
+    """(K, N, G) of a GEMM-packing layer from its tensor shapes; the library answers the shape rules itself."""
+    if groups <= 0 or rows % groups != 0:
+        raise ValueError(f"{what}: {rows} input channels do not divide into {groups} groups")
+    return rows, n8 * 8, rows // groups
+
+
+def repack_awq_gemm_to_mi355x(qweight, qzeros, scales):
+    """AWQ GEMM-packing tensors (a ``WQLinear_GEMM`` checkpoint: qweight int32 [K, N/8], qzeros int32 [K/G, N/8], scales fp16
+    [K/G, N]) -> (qweight, scales, qzeros) in MI355X order, on the GPU.  The outputs have ``padded_in_features(K, G)`` rows'
+    worth of weights and groups (== K when K % 128 == 0); what lies beyond K contributes exactly 0."""
+    fn_name = "quick_repack_awq_gemm_to_mi355x"
+    for t, d, nm in ((qweight, torch.int32, "qweight"), (qzeros, torch.int32, "qzeros"), (scales, torch.float16, "scales")):
+        _expect(t, d, nm)
+    K, N, G = _awq_gemm_dims(qweight.shape[0], qweight.shape[1], scales.shape[0], fn_name)
+    if tuple(qzeros.shape) != (K // G, N // 8) or tuple(scales.shape) != (K // G, N):
+        raise ValueError(f"{fn_name}: qzeros / scales must be [{K // G}, {N // 8}] / [{K // G}, {N}] for K={K} N={N} G={G}, "
+                         f"got {tuple(qzeros.shape)} / {tuple(scales.shape)}")
+    lib = _lib.load()
+    Kp = lib.quick_padded_in_features(K, G) or K      # (0: a shape the call below refuses before it touches the outputs)
+    dev = qweight.device
+    outs = [torch.empty((Kp // 4, N // 2), dtype=torch.int32, device=dev),
+            torch.empty((Kp // G, 2 * N), dtype=torch.float16, device=dev),
+            torch.empty((Kp // G, N // 4), dtype=torch.int32, device=dev)]
+    with torch.cuda.device(dev):
+        rc = lib.quick_repack_awq_gemm_to_mi355x(qweight.data_ptr(), qzeros.data_ptr(), scales.data_ptr(),
+                                                 outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), K, N, G, _stream())
+    if rc != _OK:
+        _raise(rc)
+    return tuple(outs)
+
+
+def repack_mi355x_to_awq_gemm(qweight, scales, qzeros, in_features=None):
+    """MI355X-order tensors -> (qweight, qzeros, scales) in the AWQ GEMM packing, on the GPU.  in_features % 128 == 0: a padded copy
+    (``in_features``, the layer's own, smaller than the tensors' rows) is never turned back -- NotImplementedError."""
+    fn_name = "quick_repack_mi355x_to_awq_gemm"
+    for t, d, nm in ((qweight, torch.int32, "qweight"), (scales, torch.float16, "scales"), (qzeros, torch.int32, "qzeros")):
+        _expect(t, d, nm)
+    K, N, G = _awq_gemm_dims(qweight.shape[0] * 4, qweight.shape[1] // 4, scales.shape[0], fn_name)
+    if in_features is not None and in_features != K:
+        if in_features % 128 == 0:
+            raise ValueError(f"{fn_name}: the tensors hold {K} input channels, not {in_features}")
+        K = in_features                                # (the library refuses it before it touches a tensor)
+    NG = scales.shape[0]
+    if tuple(scales.shape) != (NG, 2 * N) or tuple(qzeros.shape) != (NG, N // 4):
+        raise ValueError(f"{fn_name}: scales / qzeros must be [{NG}, {2 * N}] / [{NG}, {N // 4}] for N={N} G={G}, "
+                         f"got {tuple(scales.shape)} / {tuple(qzeros.shape)}")
+    dev = qweight.device
+    outs = [torch.empty((K, N // 8), dtype=torch.int32, device=dev),
+            torch.empty((K // G, N // 8), dtype=torch.int32, device=dev),
+            torch.empty((K // G, N), dtype=torch.float16, device=dev)]
+    with torch.cuda.device(dev):
+        rc = _lib.load().quick_repack_mi355x_to_awq_gemm(qweight.data_ptr(), scales.data_ptr(), qzeros.data_ptr(),
+                                                         outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), K, N, G, _stream())
+    if rc != _OK:
+        _raise(rc)
+    return tuple(outs)
+
+
 def dequantize_mi355x(qweight, scales, qzeros):
     """Dense fp16 [K, N] = fp16((w - z) * s) from MI355X-order tensors (parity aid)."""
     lib = _lib.load()

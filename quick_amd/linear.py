@@ -149,6 +149,30 @@ class WQLinear_QUICK(nn.Module):
             awq_linear._set_packed(*packing.pack_cuda_order(intweight, s, z), prepared=False)
         return awq_linear
 
+    @classmethod
+    def from_awq_gemm(cls, src, k_split_1=2, k_split_2=8):
+        """A prepared WQLinear_QUICK of the layer an AWQ GEMM-packing module holds -- ``quick_amd.WQLinear_GEMM``, or any module with the
+        reference's buffers qweight [K, N/8] / qzeros [K/G, N/8] / scales [K/G, N] / bias (quick/awq/modules/linear/gemm.py:29-63).  Shares
+        no storage with ``src``; its ``state_dict()`` is the QUICK checkpoint of the same layer.  in_features % 128 != 0: as from_linear,
+        the buffers hold the reference's QUICK order."""
+        ours = hasattr(src, "awq_gemm_order")
+        K, N = src.in_features, src.out_features
+        bias = getattr(src, "bias", None)
+        m = cls(src.w_bit, src.group_size, K, N, bias is not None, src.qweight.device, k_split_1, k_split_2)
+        if bias is not None:
+            m.bias = bias.clone().half()
+        if ours and src.is_prepared:                                  # already MI355X order: the same bits
+            m._set_packed(src.qweight.clone(), src.scales.clone(), src.qzeros.clone(), prepared=True)
+            return m
+        qw, qz, sc = src.qweight, src.qzeros, src.scales
+        if K % 128 != 0:
+            m._set_packed(*packing.awq_gemm_to_cuda_order(qw, qz, sc), prepared=False)
+        elif qw.is_cuda:
+            m._set_packed(*kernels.repack_awq_gemm_to_mi355x(qw.contiguous(), qz.contiguous(), sc.contiguous()), prepared=True)
+        else:
+            m._set_packed(*packing.awq_gemm_to_mi355x(qw, qz, sc), prepared=True)
+        return m
+
     # ---------------------------------------------------------------- forward
     @torch.no_grad()
     def forward(self, x):

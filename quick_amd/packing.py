@@ -7,6 +7,9 @@ the gfx950 kernels consume.  Logical tensors:
     iw [K, N] int (0..15)     s [K/G, N] fp16     z [K/G, N] int (0..15)
 
 "cuda order"   = byte-for-byte the reference's packed tensors / checkpoint format.
+"awq gemm"     = the packing of the reference's WQLinear_GEMM (gemm.py:29-63, 108-143), which published AWQ checkpoints
+                 use: qweight int32 [K, N/8] and qzeros int32 [K/G, N/8] with nibble i of dword c = channel
+                 8c + [0,2,4,6,1,3,5,7][i], scales fp16 [K/G, N] plain.  Tensor order: (qweight, qzeros, scales).
 "mi355x order" = same shapes and dtypes, elements permuted for the v_mfma_f32_16x16x32_f16 A-operand
                  fragment (DESIGN.md "Data layout"): tile (n/16, k/128) is 1 KiB contiguous, lane
                  (n%16) + 16*((k%32)/8) owns 16 bytes = the dwords of 4 consecutive k-steps, and inside
@@ -15,7 +18,8 @@ the gfx950 kernels consume.  Logical tensors:
 import torch
 
 __all__ = ["quantize_intweight", "pack_cuda_order", "unpack_cuda_order", "pack_mi355x", "unpack_mi355x",
-           "cuda_to_mi355x", "mi355x_to_cuda"]
+           "cuda_to_mi355x", "mi355x_to_cuda", "pack_awq_gemm", "unpack_awq_gemm", "awq_gemm_to_mi355x", "mi355x_to_awq_gemm",
+           "awq_gemm_to_cuda_order", "padded_in_features"]
 
 
 def quantize_intweight(weight, scales, zeros, group_size):
@@ -182,3 +186,69 @@ def cuda_to_mi355x(qweight, qscales, qzeros):
 
 def mi355x_to_cuda(qweight, qscales, qzeros):
     return pack_cuda_order(*unpack_mi355x(qweight, qscales, qzeros))
+
+
+# ---------------------------------------------------------------------------------------------- AWQ GEMM packing
+_AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)      # nibble i of a dword holds channel 8c + _AWQ_ORDER[i] (gemm.py:116)
+
+
+def _pack_awq(a):
+    """[R, N] 4-bit values -> int32 [R, N/8] in the AWQ nibble order."""
+    R, N = a.shape
+    if N % 8 != 0:
+        raise ValueError("OC is not multiple of pack_num = 8")
+    v = (a.to(torch.int64) & 15).reshape(R, N // 8, 8)[:, :, list(_AWQ_ORDER)]
+    return _to_i32((v << (4 * _arange(8, a.device))).sum(dim=2))
+
+
+def _unpack_awq(q):
+    """int32 [R, N/8] -> uint8 [R, N]."""
+    nib = (_as_u32(q)[:, :, None] >> (4 * _arange(8, q.device))) & 15        # [R, N/8, 8]: slot i = channel 8c + order[i]
+    out = torch.empty_like(nib)
+    out[:, :, list(_AWQ_ORDER)] = nib
+    return out.reshape(q.shape[0], -1).to(torch.uint8)
+
+
+def pack_awq_gemm(iw, s, z):
+    """Logical (iw [K, N], s [K/G, N], z [K/G, N]) -> (qweight int32 [K, N/8], qzeros int32 [K/G, N/8], scales fp16 [K/G, N]),
+    the packing of WQLinear_GEMM (checkpoint order of its three tensors)."""
+    return _pack_awq(iw), _pack_awq(z), s.to(torch.float16).contiguous()
+
+
+def unpack_awq_gemm(qweight, qzeros, scales):
+    """-> logical (iw [K, N] uint8, s [K/G, N] fp16, z [K/G, N] uint8)."""
+    return _unpack_awq(qweight), scales.to(torch.float16).contiguous(), _unpack_awq(qzeros)
+
+
+def padded_in_features(K, G):
+    """The next multiple of lcm(128, G) (quick_padded_in_features, include/quick_amd.h): the rows of the MI355X-order copy of a layer."""
+    import math
+    unit = 128 * G // math.gcd(128, G)
+    return (K + unit - 1) // unit * unit
+
+
+def _pad_rows(t, rows):
+    if rows == t.shape[0]:
+        return t
+    return torch.cat([t, torch.zeros((rows - t.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)])
+
+
+def awq_gemm_to_mi355x(qweight, qzeros, scales):
+    """GEMM-packing tensors -> (qweight, scales, qzeros) in MI355X order, as the HIP kernel writes them: Kp = padded_in_features(K, G)
+    rows, the added rows with weight 0 and the added groups with scale 0 and zero point 0 (Kp == K when K % 128 == 0)."""
+    iw, s, z = unpack_awq_gemm(qweight, qzeros, scales)
+    K, N = iw.shape
+    _check(K, N, False)
+    G = K // s.shape[0]
+    Kp = padded_in_features(K, G)
+    return pack_mi355x(_pad_rows(iw, Kp), _pad_rows(s, Kp // G), _pad_rows(z, Kp // G))
+
+
+def mi355x_to_awq_gemm(qweight, qscales, qzeros):
+    """MI355X-order tensors -> (qweight, qzeros, scales) in the GEMM packing."""
+    return pack_awq_gemm(*unpack_mi355x(qweight, qscales, qzeros))
+
+
+def awq_gemm_to_cuda_order(qweight, qzeros, scales):
+    """Checkpoint conversion: GEMM packing -> the QUICK packing (qweight, scales, qzeros) of the same layer."""
+    return pack_cuda_order(*unpack_awq_gemm(qweight, qzeros, scales))

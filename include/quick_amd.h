@@ -322,6 +322,28 @@ int quick_repack_mi355x_to_awq_gemm(const void* qweight_in, const void* scales_i
                                     void* qweight_out, void* qzeros_out, void* scales_out,
                                     int K, int N, int group_size, void* hip_stream);
 
+/*
+ * gate_proj and up_proj of an MLP <-> the one layer the silu_mul epilogue of quick_w4a16_gemm_f16_fused reads, whose 2 * I output
+ * channels interleave gate and up in blocks of 8: fused channel 16t + i = gate channel 8t + i, fused channel 16t + 8 + i = up channel
+ * 8t + i (i < 8).  Everything is in mi355x order, where the interleave moves whole 16-byte pieces and no nibble changes place:
+ *   per projection   qweight [K/4, I/2]   scales [K/G, 2I]   qzeros [K/G, I/4]
+ *   fused            qweight [K/4, I]     scales [K/G, 4I]   qzeros [K/G, I/2]
+ * quick_split_gate_up_mi355x is the exact inverse (saving).  One launch each, 16-byte loads and stores, every output byte written
+ * once -- the second half of every qzeros row, which holds no channels, as 0 -- with no atomics, memset or LDS.  Inputs and outputs
+ * must not alias; every pointer must be 16-byte aligned.  Answered before any GPU work, with a sentence in quick_amd_last_error():
+ *   K, I or G <= 0, G % 32 != 0, K % G != 0, I % 8 != 0, a null or misaligned pointer    QUICK_ERR_INVALID_ARGUMENT
+ *   K % 128 != 0 (a padded layer has no mi355x order of its own), I % 64 != 0            QUICK_ERR_UNSUPPORTED
+ * (2 * I % 128 == 0 is the GEMM kernels' rule for the fused layer's width; the shape rules are answered before the pointers are looked at).
+ */
+int quick_interleave_gate_up_mi355x(const void* gate_qweight, const void* gate_scales, const void* gate_qzeros,
+                                    const void* up_qweight, const void* up_scales, const void* up_qzeros,
+                                    void* qweight_out, void* scales_out, void* qzeros_out,
+                                    int K, int I, int group_size, void* hip_stream);
+int quick_split_gate_up_mi355x(const void* qweight_in, const void* scales_in, const void* qzeros_in,
+                               void* gate_qweight, void* gate_scales, void* gate_qzeros,
+                               void* up_qweight, void* up_scales, void* up_qzeros,
+                               int K, int I, int group_size, void* hip_stream);
+
 /* Dequantise an MI355X-order layer to a dense fp16 [K, N] row-major matrix (debug / parity aid;
  * counterpart of the reference CPU path quick/awq/utils/packing_utils.py:82-97). */
 int quick_dequantize_mi355x_f16(const void* qweight, const void* scales, const void* qzeros,

@@ -43,6 +43,8 @@ _SIGNATURES = {
     "quick_repack_cuda_to_mi355x_padded": (_I, [_P] * 6 + [_I, _I, _I, _P]),
     "quick_repack_awq_gemm_to_mi355x": (_I, [_P] * 6 + [_I, _I, _I, _P]),
     "quick_repack_mi355x_to_awq_gemm": (_I, [_P] * 6 + [_I, _I, _I, _P]),
+    "quick_interleave_gate_up_mi355x": (_I, [_P] * 9 + [_I, _I, _I, _P]),
+    "quick_split_gate_up_mi355x": (_I, [_P] * 9 + [_I, _I, _I, _P]),
     "quick_dequantize_mi355x_f16": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)

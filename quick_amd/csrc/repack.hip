@@ -4,6 +4,7 @@
 // w4a16_gemm.hip ("mi355x order").  One-time, load-side work: gather kernels, one thread per
 // output dword.
 #include "w4a16_common.hpp"
+#include "gate_up_mi355x.hpp"
 #include "../../include/quick_amd.h"
 
 #include <cstdio>
@@ -231,6 +232,25 @@ __global__ __launch_bounds__(256) void repack_sz_mi355x_to_awq_gemm(const uint32
   z_out[i] = z;
 }
 
+// ------------------------------------------------------------------------------------------------
+// gate_proj / up_proj <-> the fused layer of the silu_mul epilogue (output channels: gate and up interleaved in blocks of 8), all in mi355x
+// order.  In this order the interleave moves whole 16-byte pieces: with the weights viewed as pieces
+// [channel tile of 16][k tile][quarter q = (k % 32) / 8][c = n % 16], fused piece (T, kt, q, c) is piece (T / 2, kt, q, 8 * (T % 2) + c % 8) of
+// gate (c < 8) or up (c >= 8); the scale words [channel tile][group][16] follow the same rule, four words to a piece; the plain zero-point
+// copy interleaves dwords (eight channels each) in the first half of a row and is 0 in the second.  One lane per fused piece, the same
+// index in both directions -- kSplit only turns the copy round -- and one launch for the three tensors: workgroups [0, wblocks) move weights,
+// [wblocks, wblocks + sblocks) scale words, the rest zero points.  The lane's work is gate_up_mi355x_lane (gate_up_mi355x.hpp), which a host
+// program can run too (tools/gate_up_host_check.py: every index under the address sanitizer).
+// ------------------------------------------------------------------------------------------------
+template <bool kSplit>
+__global__ __launch_bounds__(256) void gate_up_mi355x(u32x4* __restrict__ gate_qw, u32x4* __restrict__ gate_sc, u32x4* __restrict__ gate_qz,
+                                                      u32x4* __restrict__ up_qw, u32x4* __restrict__ up_sc, u32x4* __restrict__ up_qz,
+                                                      u32x4* __restrict__ fused_qw, u32x4* __restrict__ fused_sc, u32x4* __restrict__ fused_qz,
+                                                      int K, int I, int NG, unsigned wblocks, unsigned sblocks) {
+  gate_up_mi355x_lane<kSplit>(gate_qw, gate_sc, gate_qz, up_qw, up_sc, up_qz, fused_qw, fused_sc, fused_qz, K, I, NG, wblocks, sblocks,
+                              blockIdx.x, threadIdx.x);
+}
+
 static int check(int K, int N, int G) {
   if (K <= 0 || N <= 0 || G <= 0 || N % 128 != 0 || G % 32 != 0 || K % G != 0) return QUICK_ERR_INVALID_ARGUMENT;
   if (K % 128 != 0) return QUICK_ERR_UNSUPPORTED;
@@ -346,6 +366,68 @@ int quick_repack_mi355x_to_awq_gemm(const void* qweight_in, const void* scales_i
   hipLaunchKernelGGL(repack_sz_mi355x_to_awq_gemm, dim3((unsigned)(((size_t)NG * (N / 8) + 255) / 256)), dim3(256), 0, st,
                      (const uint32_t*)scales_in, (half_t*)scales_out, (uint32_t*)qzeros_out, NG, N);
   return hipGetLastError() == hipSuccess ? QUICK_OK : set_last_error(QUICK_ERR_LAUNCH, "quick_repack_mi355x_to_awq_gemm: launch failed");
+}
+
+}  // extern "C"
+
+// shape rules of the gate/up interleave, answered before any GPU work (include/quick_amd.h)
+static int check_gate_up(const char* fn, int K, int I, int G) {
+  char text[256];
+  const char* why = nullptr;
+  int code = QUICK_ERR_INVALID_ARGUMENT;
+  if (K <= 0 || I <= 0 || G <= 0) why = "non-positive dimension";
+  else if (G % 32 != 0) why = "Group size should be a multiple of 32";
+  else if (K % G != 0) why = "in_features is not a multiple of the group size";
+  else if (I % 8 != 0) why = "intermediate size is not multiple of pack_num = 8";
+  else {
+    code = QUICK_ERR_UNSUPPORTED;
+    if (K % 128 != 0) why = "in_features must be a multiple of 128: gate and up are interleaved in MI355X order, which a padded layer does not have";
+    else if (I % 64 != 0) why = "intermediate size must be a multiple of 64: the fused layer's 2 * I channels must be a multiple of 128 for the MI355X GEMM kernels";
+  }
+  if (!why) return QUICK_OK;
+  snprintf(text, sizeof(text), "%s: %s (K=%d I=%d G=%d)", fn, why, K, I, G);
+  return set_last_error(code, text);
+}
+
+template <bool kSplit>
+static int launch_gate_up(const char* fn, void* const (&t)[9], int K, int I, int G, void* hip_stream) {
+  if (int rc = check_gate_up(fn, K, I, G)) return rc;
+  char text[128];
+  for (void* p : t) {
+    if (p && ((uintptr_t)p & 15) == 0) continue;
+    snprintf(text, sizeof(text), "%s: %s", fn, p ? "tensor pointers must be 16-byte aligned" : "null tensor pointer");
+    return set_last_error(QUICK_ERR_INVALID_ARGUMENT, text);
+  }
+  const int NG = K / G;
+  if (((size_t)K * I / 16 + (size_t)NG * I / 2 + (size_t)NG * (I / 16)) / 256 + 3 > 0x7fffffffu) {     // (Llama-2-70B: 57.8 k workgroups)
+    snprintf(text, sizeof(text), "%s: the layer needs more workgroups than one grid dimension holds", fn);
+    return set_last_error(QUICK_ERR_UNSUPPORTED, text);
+  }
+  const unsigned wblocks = (unsigned)(((size_t)K * I / 16 + 255) / 256), sblocks = (unsigned)(((size_t)NG * I / 2 + 255) / 256);
+  const unsigned zblocks = (unsigned)(((size_t)NG * (I / 16) + 255) / 256);
+  hipLaunchKernelGGL(gate_up_mi355x<kSplit>, dim3(wblocks + sblocks + zblocks), dim3(256), 0, (hipStream_t)hip_stream, (u32x4*)t[0], (u32x4*)t[1],
+                     (u32x4*)t[2], (u32x4*)t[3], (u32x4*)t[4], (u32x4*)t[5], (u32x4*)t[6], (u32x4*)t[7], (u32x4*)t[8], K, I, NG, wblocks, sblocks);
+  if (hipGetLastError() == hipSuccess) return QUICK_OK;
+  snprintf(text, sizeof(text), "%s: launch failed", fn);
+  return set_last_error(QUICK_ERR_LAUNCH, text);
+}
+
+extern "C" {
+
+int quick_interleave_gate_up_mi355x(const void* gate_qweight, const void* gate_scales, const void* gate_qzeros, const void* up_qweight,
+                                    const void* up_scales, const void* up_qzeros, void* qweight_out, void* scales_out, void* qzeros_out,
+                                    int K, int I, int group_size, void* hip_stream) {
+  void* const t[9] = {(void*)gate_qweight, (void*)gate_scales, (void*)gate_qzeros, (void*)up_qweight, (void*)up_scales, (void*)up_qzeros,
+                      qweight_out, scales_out, qzeros_out};
+  return launch_gate_up<false>("quick_interleave_gate_up_mi355x", t, K, I, group_size, hip_stream);
+}
+
+int quick_split_gate_up_mi355x(const void* qweight_in, const void* scales_in, const void* qzeros_in, void* gate_qweight, void* gate_scales,
+                               void* gate_qzeros, void* up_qweight, void* up_scales, void* up_qzeros, int K, int I, int group_size,
+                               void* hip_stream) {
+  void* const t[9] = {gate_qweight, gate_scales, gate_qzeros, up_qweight, up_scales, up_qzeros,
+                      (void*)qweight_in, (void*)scales_in, (void*)qzeros_in};
+  return launch_gate_up<true>("quick_split_gate_up_mi355x", t, K, I, group_size, hip_stream);
 }
 
 }  // extern "C"

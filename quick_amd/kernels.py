@@ -372,6 +372,80 @@ def repack_mi355x_to_awq_gemm(qweight, scales, qzeros, in_features=None):
     return tuple(outs)
 
 
+def gate_up_shape_check(K, I, G):
+    """The shape rules of the gate / up interleave (include/quick_amd.h), answered by the library without a GPU: NotImplementedError with
+    its sentence outside the envelope (K % 128, I % 64), ValueError for a shape that is no layer at all."""
+    rc = _lib.load().quick_interleave_gate_up_mi355x(*([None] * 9), K, I, G, None)
+    if rc != _OK and "null tensor pointer" not in _lib.last_error():      # (the rules come first; with them met, the pointers are all it can object to)
+        _raise(rc)
+
+
+def _gate_up_triple(t, I, width, what):
+    """dtype, device, contiguity and shape of one MI355X-order (qweight, scales, qzeros) of `width` * I channels; -> (K, NG)."""
+    qweight, scales, qzeros = t
+    for x, d, nm in ((qweight, torch.int32, "qweight"), (scales, torch.float16, "scales"), (qzeros, torch.int32, "qzeros")):
+        _expect(x, d, f"{what} {nm}")
+        if x.dim() != 2 or x.device != qweight.device:
+            raise ValueError(f"{what} {nm} must be a 2-D tensor on {qweight.device}")
+    K, NG = qweight.shape[0] * 4, scales.shape[0]
+    want = ((K // 4, I // 2 * width), (NG, 2 * I * width), (NG, I // 4 * width))
+    if tuple(tuple(x.shape) for x in t) != want:
+        raise ValueError(f"{what}: qweight / scales / qzeros must be {' / '.join(str(list(w)) for w in want)}, got "
+                         f"{' / '.join(str(list(x.shape)) for x in t)}")
+    return K, NG
+
+
+def _gate_up_call(fn_name, tensors, K, I, NG):
+    """``tensors``: the nine of the C signature, in its order."""
+    if NG <= 0 or K % NG != 0:
+        raise ValueError(f"{fn_name}: {K} input channels do not divide into {NG} groups")
+    with torch.cuda.device(tensors[0].device):
+        rc = getattr(_lib.load(), fn_name)(*[x.data_ptr() for x in tensors], K, I, K // NG, _stream())
+    if rc != _OK:
+        _raise(rc)
+
+
+def _empty_gate_up(K, I, NG, width, dev):
+    return (torch.empty((K // 4, I // 2 * width), dtype=torch.int32, device=dev),
+            torch.empty((NG, 2 * I * width), dtype=torch.float16, device=dev),
+            torch.empty((NG, I // 4 * width), dtype=torch.int32, device=dev))
+
+
+def interleave_gate_up_mi355x(gate, up, out=None):
+    """MI355X-order (qweight, scales, qzeros) of gate_proj and of up_proj -> those of the [K, 2I] layer whose output channels interleave
+    gate and up in blocks of 8, which ``gemm_forward(..., silu_mul=True)`` reads; one HIP launch.  ``out`` (optional): the three tensors
+    to write, which must not share memory with the inputs."""
+    fn_name = "quick_interleave_gate_up_mi355x"
+    gate, up = tuple(gate), tuple(up)
+    I = gate[0].shape[1] * 2
+    K, NG = _gate_up_triple(gate, I, 1, "gate")
+    if _gate_up_triple(up, I, 1, "up") != (K, NG) or up[0].device != gate[0].device:
+        raise ValueError(f"{fn_name}: gate and up must be layers of the same shape on the same device")
+    if out is None:
+        out = _empty_gate_up(K, I, NG, 2, gate[0].device)
+    elif _gate_up_triple(tuple(out), I, 2, "out") != (K, NG) or out[0].device != gate[0].device:
+        raise ValueError(f"{fn_name}: out must be the fused layer of the same K and groups on the same device")
+    _gate_up_call(fn_name, gate + up + tuple(out), K, I, NG)
+    return tuple(out)
+
+
+def split_gate_up_mi355x(qweight, scales, qzeros, out=None):
+    """The inverse of interleave_gate_up_mi355x (saving): -> ((qweight, scales, qzeros) of gate, the same of up).  ``out``: the two
+    triples to write."""
+    fn_name = "quick_split_gate_up_mi355x"
+    fused = (qweight, scales, qzeros)
+    I = qweight.shape[1]
+    K, NG = _gate_up_triple(fused, I, 2, "fused")
+    if out is None:
+        out = (_empty_gate_up(K, I, NG, 1, qweight.device), _empty_gate_up(K, I, NG, 1, qweight.device))
+    gate, up = tuple(out[0]), tuple(out[1])
+    for t, what in ((gate, "out gate"), (up, "out up")):
+        if _gate_up_triple(t, I, 1, what) != (K, NG) or t[0].device != qweight.device:
+            raise ValueError(f"{fn_name}: {what} must be a projection of the same K and groups on the same device")
+    _gate_up_call(fn_name, fused + gate + up, K, I, NG)
+    return gate, up
+
+
 def dequantize_mi355x(qweight, scales, qzeros):
     """Dense fp16 [K, N] = fp16((w - z) * s) from MI355X-order tensors (parity aid)."""
     lib = _lib.load()

@@ -19,7 +19,7 @@ import torch
 
 __all__ = ["quantize_intweight", "pack_cuda_order", "unpack_cuda_order", "pack_mi355x", "unpack_mi355x",
            "cuda_to_mi355x", "mi355x_to_cuda", "pack_awq_gemm", "unpack_awq_gemm", "awq_gemm_to_mi355x", "mi355x_to_awq_gemm",
-           "awq_gemm_to_cuda_order", "padded_in_features"]
+           "awq_gemm_to_cuda_order", "padded_in_features", "interleave8", "interleave_gate_up_mi355x", "split_gate_up_mi355x"]
 
 
 def quantize_intweight(weight, scales, zeros, group_size):
@@ -252,3 +252,51 @@ def mi355x_to_awq_gemm(qweight, qscales, qzeros):
 def awq_gemm_to_cuda_order(qweight, qzeros, scales):
     """Checkpoint conversion: GEMM packing -> the QUICK packing (qweight, scales, qzeros) of the same layer."""
     return pack_cuda_order(*unpack_awq_gemm(qweight, qzeros, scales))
+
+
+# ---------------------------------------------------------------------------------------------- gate / up of the silu_mul epilogue
+def interleave8(a, b):
+    """[.., I] x 2 -> [.., 2I] with out[16t + i] = a[8t + i], out[16t + 8 + i] = b[8t + i] (i < 8): the channel order of the GEMM's silu_mul
+    epilogue (gate and up in blocks of 8)."""
+    if a.shape != b.shape or a.shape[-1] % 8 != 0:
+        raise ValueError("interleave8: two tensors of the same shape, the last dimension a multiple of 8")
+    lead = a.shape[:-1]
+    return torch.stack([a.reshape(*lead, -1, 8), b.reshape(*lead, -1, 8)], dim=-2).reshape(*lead, -1)
+
+
+def _gate_up_dims(qweight, scales, qzeros, fused):
+    """(K, I, NG) of MI355X-order tensors of one projection (or of the fused layer), the envelope of the HIP kernels checked."""
+    K, I = qweight.shape[0] * 4, qweight.shape[1] * (1 if fused else 2)
+    NG = scales.shape[0]
+    if K % 128 != 0 or I % 64 != 0:
+        raise ValueError("gate / up interleave: in_features must be a multiple of 128 and the intermediate size a multiple of 64")
+    width = 2 if fused else 1
+    if tuple(scales.shape) != (NG, 2 * I * width) or tuple(qzeros.shape) != (NG, I // 4 * width):
+        raise ValueError(f"scales / qzeros must be [{NG}, {2 * I * width}] / [{NG}, {I // 4 * width}], got {tuple(scales.shape)} / {tuple(qzeros.shape)}")
+    return K, I, NG
+
+
+def interleave_gate_up_mi355x(gate, up):
+    """MI355X-order (qweight, scales, qzeros) of gate_proj and of up_proj -> those of the layer with channels interleave8(gate, up), in
+    packed space: == pack_mi355x of the interleaved logical layers.  Weights are 16-byte pieces [channel tile of 16][k tile][quarter][16],
+    scale words [channel tile][group][16]; fused tile T takes half T % 2 of tile T / 2 of either projection, gate's in front of up's
+    (quick_interleave_gate_up_mi355x, include/quick_amd.h)."""
+    K, I, NG = _gate_up_dims(*gate, fused=False)
+    if any(a.shape != b.shape or a.dtype != b.dtype for a, b in zip(gate, up)):
+        raise ValueError("gate and up must have the same shapes and dtypes")
+    qw = torch.stack([t.reshape(I // 16, K // 128, 4, 2, 8, 4) for t in (gate[0], up[0])], dim=4)         # (T', kt, q, T % 2, gate | up, c % 8, dword)
+    qw = qw.permute(0, 3, 1, 2, 4, 5, 6).reshape(K // 4, I)
+    sc = torch.stack([t.contiguous().view(torch.int32).reshape(I // 16, NG, 2, 8) for t in (gate[1], up[1])], dim=3)   # (T', g, T % 2, gate | up, c % 8)
+    sc = sc.permute(0, 2, 1, 3, 4).reshape(NG, 2 * I).view(torch.float16)
+    qz = torch.stack([gate[2][:, :I // 8], up[2][:, :I // 8]], dim=2).reshape(NG, I // 4)
+    return qw, sc, torch.cat([qz, torch.zeros_like(qz)], dim=1)
+
+
+def split_gate_up_mi355x(qweight, scales, qzeros):
+    """The inverse of interleave_gate_up_mi355x: -> ((qweight, scales, qzeros) of gate, the same of up)."""
+    K, I, NG = _gate_up_dims(qweight, scales, qzeros, fused=True)
+    qw = qweight.reshape(I // 16, 2, K // 128, 4, 2, 8, 4).permute(4, 0, 2, 3, 1, 5, 6).reshape(2, K // 4, I // 2)
+    sc = scales.contiguous().view(torch.int32).reshape(I // 16, 2, NG, 2, 8).permute(3, 0, 2, 1, 4).reshape(2, NG, I).view(torch.float16)
+    qz = qzeros[:, :I // 4].reshape(NG, I // 8, 2).permute(2, 0, 1)
+    qz = torch.cat([qz, torch.zeros_like(qz)], dim=2)
+    return tuple((qw[h].contiguous(), sc[h].contiguous(), qz[h].contiguous()) for h in (0, 1))

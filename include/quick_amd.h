@@ -255,6 +255,26 @@ int quick_decode_rope_attention_f16(const void* qkv, const void* cos_table, cons
  * refusals as the launch.  For logs and for tests of the dispatch; the wording may grow fields, the leading kernel word will not change. */
 int quick_decode_rope_attention_describe(int batch, int n_heads, int n_kv_heads, int head_dim, int cache_len, char* text,
                                          size_t text_bytes);
+/* Causal attention of `tokens` new tokens per sequence over the KV cache (prefill from any position: first prompt, second chat turn,
+ * chunked prefill, speculative verify), D == 128, GQA aware, one launch.
+ *   q        [batch, n_heads, tokens, D]: what quick_rope_kv_write_f16 writes to q_out
+ *   caches   [batch, n_kv_heads, cache_len, D]; rows *pos0 .. *pos0 + tokens - 1 already written (by that same call).  Read, never written.
+ *   pos0     DEVICE pointer to one int64 (no host read: the launch can be captured); the caller keeps 0 <= *pos0, *pos0 + tokens <= cache_len
+ *   out      [batch * tokens, n_heads * D], row b * tokens + t: the matrix o_proj's GEMM consumes
+ * Query t attends cache rows 0 .. *pos0 + t and nothing else.  Rows at or behind *pos0 + tokens may hold anything (NaN, +-Inf): they are
+ * never read.  Online softmax, no score matrix in memory, no workspace, no atomics.  Both products run on the matrix core
+ * (v_mfma_f32_16x16x32_f16) with fp32 accumulation; scores, running max and running sum in fp32; THE WEIGHTS P ARE ROUNDED TO FP16 as the
+ * operand of the second product; one fp32 division and one rounding to fp16 at the end.
+ * Answered before any GPU work, with a sentence in quick_amd_last_error():
+ *   a null pointer; batch, tokens, n_heads, n_kv_heads or cache_len <= 0; tokens > cache_len     QUICK_ERR_INVALID_ARGUMENT
+ *   head_dim != 128; n_heads % n_kv_heads != 0; n_heads or batch > 65535 (grid dimensions)        QUICK_ERR_UNSUPPORTED */
+int quick_prefill_attention_f16(const void* q, const void* k_cache, const void* v_cache, const void* pos0, void* out, int batch,
+                                int tokens, int n_heads, int n_kv_heads, int head_dim, int cache_len, float scale, void* hip_stream);
+/* The launch of quick_prefill_attention_f16 for this shape as one line of text (host-only, no GPU needed): the kernel word, query rows
+ * per workgroup, cache rows per tile, waves and the grid, e.g. "prefill-mfma q_rows=64 kv_rows=32 waves=4 grid=2x32x64".  The same
+ * refusals as the launch (the pointers aside).  The wording may grow fields, the leading kernel word will not change. */
+int quick_prefill_attention_describe(int batch, int tokens, int n_heads, int n_kv_heads, int head_dim, int cache_len, char* text,
+                                     size_t text_bytes);
 int quick_silu_mul_f16(const void* gate_up, void* y, int rows, int intermediate, void* hip_stream);
 
 /* lm_head of a decode step with the greedy arg-max folded in (the reference: torch linear + max on the fp16 layer AWQ leaves

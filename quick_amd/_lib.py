@@ -33,6 +33,8 @@ _SIGNATURES = {
     "quick_decode_attention_f16": (_I, [_P] * 5 + [_I] * 5 + [ctypes.c_float, _P]),
     "quick_decode_rope_attention_f16": (_I, [_P] * 7 + [_I] * 5 + [ctypes.c_float, _P]),
     "quick_decode_rope_attention_describe": (_I, [_I] * 5 + [ctypes.c_char_p, _Z]),
+    "quick_prefill_attention_f16": (_I, [_P] * 5 + [_I] * 6 + [ctypes.c_float, _P]),
+    "quick_prefill_attention_describe": (_I, [_I] * 6 + [ctypes.c_char_p, _Z]),
     "quick_silu_mul_f16": (_I, [_P, _P, _I, _I, _P]),
     "quick_lm_head_workspace_bytes": (_Z, [_I]),
     "quick_lm_head_argmax_f16": (_I, [_P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _P]),

@@ -1,0 +1,119 @@
+"""``QuantAttentionFused`` for MI355X: the constructor, attributes and ``forward`` triple of the reference's module
+(quick/awq/modules/fused/attn.py:100-245) on the HIP kernels of this package.  The module sits between the fused ``qkv_proj``
+(``fuse_qkv_quick`` / ``fuse_qkv_gemm``) and ``o_proj`` and owns the KV cache and the position.
+
+    one token  (T == 1)  qkv_proj | kernels.rope_attention (RoPE + cache append + single-query attention, one launch)    | o_proj
+    T > 1, any start_pos qkv_proj | kernels.rope_kv_write (RoPE + cache write) | kernels.prefill_attention (causal, MFMA) | o_proj
+
+No step reads a device value on the host and none builds a mask: the position the kernels use is a device int64 the module advances on
+the device (``start_pos`` mirrors it on the host), so a forward can be captured in a graph, and a chunk of T > 1 tokens on top of a
+non-empty cache (second chat turn, chunked prefill, speculative verify) attends the whole cache.
+
+Envelope: inference, fp16, head_dim 128, rotate-half RoPE (HF convention, the reference's ``is_neox=True``).  Where the reference rolls
+its cache, this module refuses: ``start_pos + T`` must not exceed ``max_seq_len``.
+"""
+import os
+
+import torch
+import torch.nn as nn
+
+from . import kernels
+
+HEAD_DIM = 128
+
+
+class QuantAttentionFused(nn.Module):
+    def __init__(self, hidden_size, n_heads, n_kv_heads, qkv_layer, o_proj, dev, max_seq_len, use_alibi=False, attention_shapes=None,
+                 rope_theta=10000):
+        super().__init__()
+        if use_alibi:
+            raise ValueError("QuantAttentionFused: use_alibi=True is not supported (the kernels rotate q and k, they add no ALiBi bias)")
+        if attention_shapes is not None:
+            raise ValueError("QuantAttentionFused: custom attention_shapes are not supported (the kernels take [q | k | v] of the fused qkv layer)")
+        if n_heads <= 0 or n_kv_heads <= 0 or n_heads % n_kv_heads != 0:
+            raise ValueError(f"QuantAttentionFused: n_heads ({n_heads}) must be a positive multiple of n_kv_heads ({n_kv_heads})")
+        if hidden_size % n_heads != 0 or hidden_size // n_heads != HEAD_DIM:
+            raise ValueError(f"QuantAttentionFused: head_dim must be {HEAD_DIM}, hidden_size // n_heads is {hidden_size // n_heads}")
+        width = (n_heads + 2 * n_kv_heads) * HEAD_DIM
+        if qkv_layer.out_features != width or qkv_layer.in_features != hidden_size:
+            raise ValueError(f"QuantAttentionFused: qkv_layer must map {hidden_size} to (n_heads + 2 n_kv_heads) * {HEAD_DIM} = {width} "
+                             f"channels, it maps {qkv_layer.in_features} to {qkv_layer.out_features}")
+        if o_proj.in_features != hidden_size:
+            raise ValueError(f"QuantAttentionFused: o_proj must take {hidden_size} channels, it takes {o_proj.in_features}")
+        if max_seq_len <= 0:
+            raise ValueError("QuantAttentionFused: max_seq_len must be positive")
+        self.hidden_size = hidden_size
+        self.n_heads = n_heads
+        self.n_kv_heads = n_kv_heads
+        self.n_kv_groups = n_heads // n_kv_heads
+        self.head_dim = HEAD_DIM
+        self.qkv_proj = qkv_layer
+        self.o_proj = o_proj
+        self.start_pos = 0
+        self.use_alibi = False
+        self.cache_batch_size = int(os.getenv("AWQ_BATCH_SIZE", "1"))
+        self.max_seq_len = max_seq_len
+        self.is_hf_transformers = False
+        self.rope_theta = rope_theta
+        self.rotary_dim = HEAD_DIM
+        self.is_neox = True
+        # state, not parameters: plain attributes, absent from state_dict()
+        dev = torch.device(dev)
+        inv = 1.0 / (rope_theta ** (torch.arange(0, HEAD_DIM, 2, device=dev).float() / HEAD_DIM))
+        ang = torch.outer(torch.arange(max_seq_len, device=dev).float(), inv)
+        self.cos = torch.cat((ang.cos(), ang.cos()), -1).half()
+        self.sin = torch.cat((ang.sin(), ang.sin()), -1).half()
+        self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._allocate(self.cache_batch_size, dev)
+
+    def _allocate(self, batch, dev):
+        shape = (batch, self.n_kv_heads, self.max_seq_len, HEAD_DIM)
+        self.k_cache = torch.zeros(shape, dtype=torch.float16, device=dev)
+        self.v_cache = torch.zeros(shape, dtype=torch.float16, device=dev)
+        self.cache_batch_size = batch
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        for name in ("cos", "sin", "k_cache", "v_cache"):       # (.to() / .cuda() move the state along with the projections)
+            setattr(self, name, fn(getattr(self, name)).half())
+        self.pos = fn(self.pos).to(torch.int64)
+        return self
+
+    def reset(self):
+        """Back to position 0 (the cache rows are overwritten as the positions are)."""
+        self.start_pos = 0
+        self.pos.zero_()
+
+    @torch.no_grad()
+    def forward(self, hidden_states, attention_mask=None, *args, **kwargs):
+        """hidden_states [B, T, hidden] fp16 -> (attn_output [B, T, hidden], attention_weight [B, T, hidden] = the attention output in
+        front of o_proj, past_key_value = [torch.zeros(1, 1, start_pos, 1)]), the reference's triple.
+
+        The module applies causal masking itself: ``attention_mask`` is accepted and IGNORED, as the reference's single-token path
+        ignores it; padded or ragged batches are out of scope.  A batch size other than the cache's reallocates the caches and
+        restarts at position 0, as the reference does.  ValueError where ``start_pos + T`` would exceed ``max_seq_len`` (the
+        reference rolls its cache; this module refuses)."""
+        B, T, _ = hidden_states.shape
+        if B != self.cache_batch_size:
+            self._allocate(B, self.k_cache.device)
+            self.reset()
+        if self.is_hf_transformers and "past_key_value" in kwargs and kwargs["past_key_value"] is None:
+            self.reset()                    # (the first step of a new generate())
+        if self.start_pos + T > self.max_seq_len:
+            raise ValueError(f"QuantAttentionFused: start_pos + tokens = {self.start_pos} + {T} exceeds max_seq_len = {self.max_seq_len}; "
+                             "the cache does not roll, call reset() or build the module with a larger max_seq_len")
+        if not hidden_states.is_cuda:
+            raise RuntimeError("hidden_states must be a GPU tensor: the attention kernels have no CPU implementation")
+        nh, nkv = self.n_heads, self.n_kv_heads
+        qkv = self.qkv_proj(hidden_states.reshape(B * T, self.hidden_size).contiguous())
+        att = torch.empty((B * T, nh * HEAD_DIM), dtype=torch.float16, device=qkv.device)
+        if T == 1:
+            kernels.rope_attention(qkv, self.cos, self.sin, self.pos, self.k_cache, self.v_cache, att, nh, nkv, HEAD_DIM)
+        else:
+            q = torch.empty((B, nh, T, HEAD_DIM), dtype=torch.float16, device=qkv.device)
+            kernels.rope_kv_write(qkv, self.cos, self.sin, self.pos, q, self.k_cache, self.v_cache, T, nh, nkv, HEAD_DIM)
+            kernels.prefill_attention(q, self.k_cache, self.v_cache, self.pos, att, nh, nkv, HEAD_DIM)
+        attn_output = self.o_proj(att).view(B, T, -1)
+        self.pos.add_(T)
+        self.start_pos += T
+        return attn_output, att.view(B, T, nh * HEAD_DIM), [torch.zeros(1, 1, self.start_pos, 1)]

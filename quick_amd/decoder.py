@@ -104,26 +104,34 @@ class SyntheticDecoder:
         return sum(l[k].qweight.numel() * 4 for l in self.layers for k in ("qkv", "o", "gate_up", "down"))
 
     @torch.no_grad()
-    def forward(self, tokens, pos, mask, hip_glue=True):
+    def forward(self, tokens, pos, mask, hip_glue=True, hip_attention=False, return_hidden=False):
         """tokens [B, T] int64; pos int64 [T] (positions being written); mask additive [1, 1, T, max_len] or None for
         causal prefill from position 0.  Returns the next-token ids [B] (argmax of the last position's logits).
         ``hip_glue``: RMSNorm through quick_rmsnorm_f16 and the residual adds / SiLU*mul in the GEMM epilogues (what a
-        prefill wants); False = every op around the GEMMs in eager torch (the arithmetic the tests compare against)."""
+        prefill wants); False = every op around the GEMMs in eager torch (the arithmetic the tests compare against).
+        ``hip_attention`` (with ``hip_glue`` and ``mask is None``): the prefill's attention through quick_prefill_attention_f16 instead
+        of SDPA -- no host read of the start position, and a chunk that starts behind position 0 attends the whole cache.
+        ``return_hidden``: (next tokens, the last position's normed hidden state [B, H]) instead of the tokens alone."""
         cfg, B, T = self.cfg, tokens.shape[0], tokens.shape[1]
         H, nh, nkv, D = cfg.hidden, cfg.heads, cfg.kv_heads, cfg.head_dim
         x = self.embed[tokens]                                        # [B, T, H]
         cos, sin = self.cos.index_select(0, pos), self.sin.index_select(0, pos)
         norm = (lambda v, w: kernels.rmsnorm(v.reshape(-1, H), w).view(v.shape)) if hip_glue else _rms_norm
-        p0 = int(pos[0]) if (hip_glue and mask is None) else 0   # one host read per prefill, not per layer
+        hip_attention = hip_attention and hip_glue and mask is None
+        p0 = int(pos[0]) if (hip_glue and mask is None and not hip_attention) else 0   # one host read per prefill, not per layer
         for l in self.layers:
             h = norm(x, l["ln1"])
             qkv = l["qkv"](h)                                          # W4A16 GEMM, M = B*T
             if hip_glue and mask is None and B * T <= 65535:           # prefill: RoPE + cache write in one launch
                 q = torch.empty((B, nh, T, D), dtype=torch.float16, device=x.device)
                 kernels.rope_kv_write(qkv.reshape(B * T, -1), self.cos, self.sin, pos[:1], q, l["k"], l["v"], T, nh, nkv, D)
-                att = F.scaled_dot_product_attention(q, l["k"][:, :, p0:p0 + T], l["v"][:, :, p0:p0 + T], is_causal=True,
-                                                     enable_gqa=nkv != nh)
-                att = att.transpose(1, 2).reshape(B * T, H)
+                if hip_attention:                                      # causal over cache rows 0 .. pos[0] + t, rows [B * T, H] as o wants them
+                    att = torch.empty((B * T, H), dtype=torch.float16, device=x.device)
+                    kernels.prefill_attention(q, l["k"], l["v"], pos[:1], att, nh, nkv, D)
+                else:
+                    att = F.scaled_dot_product_attention(q, l["k"][:, :, p0:p0 + T], l["v"][:, :, p0:p0 + T], is_causal=True,
+                                                         enable_gqa=nkv != nh)
+                    att = att.transpose(1, 2).reshape(B * T, H)
                 o, gu, dn = l["o"], l["gate_up"], l["down"]
                 x2 = x.reshape(B * T, H).contiguous()
                 kernels.gemm_forward(att, o.qweight, o.scales, o.qzeros, residual=x2, out=x2)
@@ -156,8 +164,9 @@ class SyntheticDecoder:
             gate = gu[..., 0, :].reshape(B, T, cfg.intermediate)           # gate/up channels interleaved in blocks of 8
             up = gu[..., 1, :].reshape(B, T, cfg.intermediate)
             x = x + l["down"](F.silu(gate) * up)                       # W4A16 GEMM
-        logits = norm(x[:, -1], self.norm) @ self.lm_head.t()
-        return logits.argmax(-1)
+        hidden = norm(x[:, -1].contiguous(), self.norm)              # (a strided view: quick_rmsnorm_f16 takes contiguous rows)
+        logits = hidden @ self.lm_head.t()
+        return (logits.argmax(-1), hidden) if return_hidden else logits.argmax(-1)
 
 
 def _gemm(m: WQLinear_QUICK, x, out, residual=None):

@@ -495,6 +495,31 @@ def rope_kv_write(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, toke
     return q_out
 
 
+def prefill_attention(q, k_cache, v_cache, pos0, out, n_heads, n_kv_heads, head_dim):
+    """Causal attention of T new tokens over the cache (quick_prefill_attention_f16): q [B, nh, T, D] as rope_kv_write leaves it, caches
+    [B, nkv, L, D] with rows *pos0 .. *pos0 + T - 1 written, pos0 a device int64 -> out [B * T, nh * D] (row b * T + t).  Query t attends
+    cache rows 0 .. *pos0 + t; no host read, no mask tensor."""
+    for t, name in ((q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (out, "out")):
+        _expect(t, torch.float16, name)
+    _expect(pos0, torch.int64, "pos0")
+    lib = _lib.load()
+    rc = lib.quick_prefill_attention_f16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), pos0.data_ptr(), out.data_ptr(),
+                                         q.shape[0], q.shape[2], n_heads, n_kv_heads, head_dim, k_cache.shape[2], head_dim ** -0.5,
+                                         _stream())
+    if rc != _OK:
+        _raise(rc)
+    return out
+
+
+def prefill_attention_describe(batch, tokens, n_heads, n_kv_heads, head_dim, cache_len):
+    """One line describing prefill_attention's launch for this shape (quick_prefill_attention_describe; host-only, no GPU needed)."""
+    buf = ctypes.create_string_buffer(128)
+    rc = _lib.load().quick_prefill_attention_describe(batch, tokens, n_heads, n_kv_heads, head_dim, cache_len, buf, len(buf))
+    if rc != _OK:
+        _raise(rc)
+    return buf.value.decode()
+
+
 def decode_attention(q, k_cache, v_cache, pos, out, n_heads, n_kv_heads, head_dim):
     """Single-query attention over cache positions 0..*pos; q [B, nh, D] -> out [B, nh * D]."""
     lib = _lib.load()

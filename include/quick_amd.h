@@ -238,6 +238,12 @@ int quick_rope_kv_append_f16(const void* qkv, const void* cos_table, const void*
 int quick_rope_kv_write_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos0, void* q_out,
                             void* k_cache, void* v_cache, int batch, int tokens, int n_heads, int n_kv_heads, int head_dim,
                             int cache_len, void* hip_stream);
+/* per-sequence form: pos0 is a DEVICE pointer to int64 [batch]; token t of sequence b sits at position pos0[b] + t.  A sequence with
+ * pos0[b] outside 0 .. cache_len - tokens is SKIPPED: its rows of q_out and of the caches are left untouched and no address outside the
+ * buffers is formed (an idle slot of a serving loop).  The same checks and error codes as quick_rope_kv_write_f16. */
+int quick_rope_kv_write_seq_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos0, void* q_out,
+                                void* k_cache, void* v_cache, int batch, int tokens, int n_heads, int n_kv_heads, int head_dim,
+                                int cache_len, void* hip_stream);
 int quick_decode_attention_f16(const void* q, const void* k_cache, const void* v_cache, const void* pos, void* out,
                                int batch, int n_heads, int n_kv_heads, int head_dim, int cache_len, float scale,
                                void* hip_stream);
@@ -249,6 +255,15 @@ int quick_decode_attention_f16(const void* q, const void* k_cache, const void* v
 int quick_decode_rope_attention_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos,
                                     void* k_cache, void* v_cache, void* out, int batch, int n_heads, int n_kv_heads,
                                     int head_dim, int cache_len, float scale, void* hip_stream);
+/* per-sequence form: pos is a DEVICE pointer to int64 [batch].  Sequence b rotates with table row pos[b], appends k and v at cache row
+ * pos[b] and attends rows 0 .. pos[b]; its workgroups sweep its own length only, so a mixed batch costs its own rows, not batch times
+ * the longest.  The kernel is chosen as for the shared form (by batch, head counts and cache_len, never by a position), and a
+ * workgroup's arithmetic is the shared launch's at *pos = pos[b], bit for bit.  A sequence with pos[b] outside 0 .. cache_len - 1 is
+ * SKIPPED: its cache rows and its row of out are left untouched (an idle slot).  The same checks and error codes as the shared form;
+ * quick_decode_rope_attention_describe serves both. */
+int quick_decode_rope_attention_seq_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos,
+                                        void* k_cache, void* v_cache, void* out, int batch, int n_heads, int n_kv_heads,
+                                        int head_dim, int cache_len, float scale, void* hip_stream);
 /* Which kernel quick_decode_rope_attention_f16 launches for this shape, as one line of text (host-only, no GPU needed): the kernel
  * ("flash", "gqa" = the vector-ALU grouped-query sweep, "gqa-mfma"), query heads per workgroup, workgroups per KV head, waves per
  * workgroup, cache rows per register set and the grid, e.g. "gqa-mfma heads=8 gsplit=1 waves=4 set_rows=64 grid=8x32".  The same
@@ -270,6 +285,12 @@ int quick_decode_rope_attention_describe(int batch, int n_heads, int n_kv_heads,
  *   head_dim != 128; n_heads % n_kv_heads != 0; n_heads or batch > 65535 (grid dimensions)        QUICK_ERR_UNSUPPORTED */
 int quick_prefill_attention_f16(const void* q, const void* k_cache, const void* v_cache, const void* pos0, void* out, int batch,
                                 int tokens, int n_heads, int n_kv_heads, int head_dim, int cache_len, float scale, void* hip_stream);
+/* per-sequence form: pos0 is a DEVICE pointer to int64 [batch]; query t of sequence b attends cache rows 0 .. pos0[b] + t, and rows at or
+ * behind pos0[b] + tokens of THAT sequence are never read.  A sequence with pos0[b] outside 0 .. cache_len - tokens is SKIPPED: its rows
+ * of out are left untouched (the shared form pulls such a value inside instead).  The same refusals and error codes as
+ * quick_prefill_attention_f16; quick_prefill_attention_describe serves both. */
+int quick_prefill_attention_seq_f16(const void* q, const void* k_cache, const void* v_cache, const void* pos0, void* out, int batch,
+                                    int tokens, int n_heads, int n_kv_heads, int head_dim, int cache_len, float scale, void* hip_stream);
 /* The launch of quick_prefill_attention_f16 for this shape as one line of text (host-only, no GPU needed): the kernel word, query rows
  * per workgroup, cache rows per tile, waves and the grid, e.g. "prefill-mfma q_rows=64 kv_rows=32 waves=4 grid=2x32x64".  The same
  * refusals as the launch (the pointers aside).  The wording may grow fields, the leading kernel word will not change. */

@@ -30,10 +30,13 @@ _SIGNATURES = {
     "quick_rmsnorm_f16": (_I, [_P, _P, _P, _I, _I, ctypes.c_float, _P]),
     "quick_rope_kv_append_f16": (_I, [_P] * 7 + [_I] * 5 + [_P]),
     "quick_rope_kv_write_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "quick_rope_kv_write_seq_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "quick_decode_attention_f16": (_I, [_P] * 5 + [_I] * 5 + [ctypes.c_float, _P]),
     "quick_decode_rope_attention_f16": (_I, [_P] * 7 + [_I] * 5 + [ctypes.c_float, _P]),
+    "quick_decode_rope_attention_seq_f16": (_I, [_P] * 7 + [_I] * 5 + [ctypes.c_float, _P]),
     "quick_decode_rope_attention_describe": (_I, [_I] * 5 + [ctypes.c_char_p, _Z]),
     "quick_prefill_attention_f16": (_I, [_P] * 5 + [_I] * 6 + [ctypes.c_float, _P]),
+    "quick_prefill_attention_seq_f16": (_I, [_P] * 5 + [_I] * 6 + [ctypes.c_float, _P]),
     "quick_prefill_attention_describe": (_I, [_I] * 6 + [ctypes.c_char_p, _Z]),
     "quick_silu_mul_f16": (_I, [_P, _P, _I, _I, _P]),
     "quick_lm_head_workspace_bytes": (_Z, [_I]),

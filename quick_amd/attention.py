@@ -11,6 +11,11 @@ non-empty cache (second chat turn, chunked prefill, speculative verify) attends 
 
 Envelope: inference, fp16, head_dim 128, rotate-half RoPE (HF convention, the reference's ``is_neox=True``).  Where the reference rolls
 its cache, this module refuses: ``start_pos + T`` must not exceed ``max_seq_len``.
+
+``per_sequence=True`` (a keyword of this package, not of the reference) gives every sequence of the batch its own position: ``pos`` is
+int64 [batch], ``forward(..., new_tokens=...)`` says how many of the T rows of each sequence are real (right-padded), and
+``reset(slots=[...])`` frees single slots.  The launches are the per-sequence forms of the same kernels; each sequence's workgroups sweep
+its own length.  ``start_pos`` is then a host-side UPPER BOUND on the largest position, not the position.
 """
 import os
 
@@ -24,7 +29,7 @@ HEAD_DIM = 128
 
 class QuantAttentionFused(nn.Module):
     def __init__(self, hidden_size, n_heads, n_kv_heads, qkv_layer, o_proj, dev, max_seq_len, use_alibi=False, attention_shapes=None,
-                 rope_theta=10000):
+                 rope_theta=10000, per_sequence=False):
         super().__init__()
         if use_alibi:
             raise ValueError("QuantAttentionFused: use_alibi=True is not supported (the kernels rotate q and k, they add no ALiBi bias)")
@@ -63,6 +68,7 @@ class QuantAttentionFused(nn.Module):
         ang = torch.outer(torch.arange(max_seq_len, device=dev).float(), inv)
         self.cos = torch.cat((ang.cos(), ang.cos()), -1).half()
         self.sin = torch.cat((ang.sin(), ang.sin()), -1).half()
+        self.per_sequence = bool(per_sequence)
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self._allocate(self.cache_batch_size, dev)
 
@@ -71,6 +77,8 @@ class QuantAttentionFused(nn.Module):
         self.k_cache = torch.zeros(shape, dtype=torch.float16, device=dev)
         self.v_cache = torch.zeros(shape, dtype=torch.float16, device=dev)
         self.cache_batch_size = batch
+        if self.per_sequence:                                   # one position per sequence, re-made with the caches
+            self.pos = torch.zeros(batch, dtype=torch.int64, device=dev)
 
     def _apply(self, fn, *args, **kwargs):
         super()._apply(fn, *args, **kwargs)
@@ -79,21 +87,61 @@ class QuantAttentionFused(nn.Module):
         self.pos = fn(self.pos).to(torch.int64)
         return self
 
-    def reset(self):
-        """Back to position 0 (the cache rows are overwritten as the positions are)."""
-        self.start_pos = 0
-        self.pos.zero_()
+    def reset(self, slots=None):
+        """Back to position 0 (the cache rows are overwritten as the positions are).  ``slots`` (``per_sequence=True`` only): the indices
+        of the sequences to restart -- a finished slot takes a new request while the others go on; ``start_pos`` is then recomputed as
+        the largest remaining position (one host read, here and nowhere in ``forward``)."""
+        if slots is None:
+            self.start_pos = 0
+            self.pos.zero_()
+            return
+        if not self.per_sequence:
+            raise ValueError("QuantAttentionFused: reset(slots=...) needs per_sequence=True (this module keeps one position for the batch)")
+        slots = [int(i) for i in slots]
+        if any(i < 0 or i >= self.cache_batch_size for i in slots):
+            raise ValueError(f"QuantAttentionFused: reset(slots={slots}): slots are 0 .. {self.cache_batch_size - 1}")
+        if slots:
+            self.pos[torch.tensor(slots, dtype=torch.int64, device=self.pos.device)] = 0
+        self.start_pos = int(self.pos.max())
+
+    def _new_tokens(self, new_tokens, B, T):
+        """-> (device int64 [B] to add to pos, or None for T everywhere; what start_pos advances by).  A list, a tuple or a CPU tensor
+        is checked here, on the host; a device tensor is taken as it is (its values are never read on the host)."""
+        if new_tokens is None:
+            return None, T
+        if isinstance(new_tokens, torch.Tensor) and new_tokens.is_cuda:
+            if new_tokens.dtype != torch.int64 or new_tokens.numel() != B or not new_tokens.is_contiguous():
+                raise ValueError(f"QuantAttentionFused: a device new_tokens must be a contiguous int64 tensor of {B} elements")
+            return new_tokens.view(B), T
+        counts = new_tokens.tolist() if isinstance(new_tokens, torch.Tensor) else list(new_tokens)
+        if len(counts) != B:
+            raise ValueError(f"QuantAttentionFused: new_tokens has {len(counts)} entries, the batch has {B} sequences")
+        if any(int(c) != c or c < 0 or c > T for c in counts):
+            raise ValueError(f"QuantAttentionFused: new_tokens must be whole numbers in 0 .. T = {T} (right-padded rows), got {counts}")
+        counts = [int(c) for c in counts]
+        return torch.tensor(counts, dtype=torch.int64), max(counts)
 
     @torch.no_grad()
-    def forward(self, hidden_states, attention_mask=None, *args, **kwargs):
+    def forward(self, hidden_states, attention_mask=None, *args, new_tokens=None, **kwargs):
         """hidden_states [B, T, hidden] fp16 -> (attn_output [B, T, hidden], attention_weight [B, T, hidden] = the attention output in
         front of o_proj, past_key_value = [torch.zeros(1, 1, start_pos, 1)]), the reference's triple.
 
         The module applies causal masking itself: ``attention_mask`` is accepted and IGNORED, as the reference's single-token path
-        ignores it; padded or ragged batches are out of scope.  A batch size other than the cache's reallocates the caches and
+        ignores it.  A batch size other than the cache's reallocates the caches and
         restarts at position 0, as the reference does.  ValueError where ``start_pos + T`` would exceed ``max_seq_len`` (the
-        reference rolls its cache; this module refuses)."""
+        reference rolls its cache; this module refuses).
+
+        Ragged batches need ``per_sequence=True``: ``new_tokens`` [B] says how many of the T rows of each sequence are real tokens
+        (0 .. T, RIGHT-padded; None: T for all).  A list, a tuple or a CPU tensor is validated on the host (ValueError); a device int64
+        [B] tensor is used as it is, without a host read, so the step can be captured in a graph.  Sequence b's rows go to cache rows
+        pos[b] .. pos[b] + T - 1 and ``pos += new_tokens`` afterwards: its padding rows lie behind its new position, where the kernels
+        never read, and the next forward overwrites them; the OUTPUT rows of padding are unspecified.  ``new_tokens[b] == 0`` is an
+        idle step, the position stays.  ``start_pos`` advances by max(new_tokens) where the counts are known on the host and by T
+        otherwise: an upper bound on the largest position, which the overflow check and ``past_key_value`` use -- a padded chunk needs
+        room for its padding.  ``attention_mask`` stays ignored in this mode too, and LEFT-padded batches are out of scope."""
         B, T, _ = hidden_states.shape
+        if new_tokens is not None and not self.per_sequence:
+            raise ValueError("QuantAttentionFused: new_tokens needs per_sequence=True (this module keeps one position for the batch)")
         if B != self.cache_batch_size:
             self._allocate(B, self.k_cache.device)
             self.reset()
@@ -101,12 +149,29 @@ class QuantAttentionFused(nn.Module):
             self.reset()                    # (the first step of a new generate())
         if self.start_pos + T > self.max_seq_len:
             raise ValueError(f"QuantAttentionFused: start_pos + tokens = {self.start_pos} + {T} exceeds max_seq_len = {self.max_seq_len}; "
-                             "the cache does not roll, call reset() or build the module with a larger max_seq_len")
+                             "the cache does not roll, call reset() or build the module with a larger max_seq_len"
+                             + ("; a padded chunk needs room for its padding (all T rows of every sequence are written), and start_pos "
+                                "is an upper bound on the positions" if self.per_sequence else ""))
+        step, advance = self._new_tokens(new_tokens, B, T) if self.per_sequence else (None, T)
         if not hidden_states.is_cuda:
             raise RuntimeError("hidden_states must be a GPU tensor: the attention kernels have no CPU implementation")
         nh, nkv = self.n_heads, self.n_kv_heads
         qkv = self.qkv_proj(hidden_states.reshape(B * T, self.hidden_size).contiguous())
         att = torch.empty((B * T, nh * HEAD_DIM), dtype=torch.float16, device=qkv.device)
+        if self.per_sequence:
+            if T == 1:
+                kernels.rope_attention(qkv, self.cos, self.sin, self.pos, self.k_cache, self.v_cache, att, nh, nkv, HEAD_DIM, per_sequence=True)
+            else:
+                q = torch.empty((B, nh, T, HEAD_DIM), dtype=torch.float16, device=qkv.device)
+                kernels.rope_kv_write(qkv, self.cos, self.sin, self.pos, q, self.k_cache, self.v_cache, T, nh, nkv, HEAD_DIM, per_sequence=True)
+                kernels.prefill_attention(q, self.k_cache, self.v_cache, self.pos, att, nh, nkv, HEAD_DIM, per_sequence=True)
+            attn_output = self.o_proj(att).view(B, T, -1)
+            if step is None:
+                self.pos.add_(T)
+            else:
+                self.pos.add_(step.to(self.pos.device, non_blocking=True))
+            self.start_pos += advance
+            return attn_output, att.view(B, T, nh * HEAD_DIM), [torch.zeros(1, 1, self.start_pos, 1)]
         if T == 1:
             kernels.rope_attention(qkv, self.cos, self.sin, self.pos, self.k_cache, self.v_cache, att, nh, nkv, HEAD_DIM)
         else:

@@ -103,12 +103,19 @@ __global__ __launch_bounds__(64) void rope_kv_kernel(const half_t* __restrict__ 
 
 // Prefill form of the kernel above: T consecutive tokens per sequence, positions *pos0 .. *pos0 + T - 1.  qkv [B * T, (nh + 2 nkv) * D]
 // (row b * T + t); q goes to q_out [B, nh, T, D] (the layout attention wants), k and v to the caches at their positions.
+// SEQ: pos0 holds one start per sequence, token t of sequence b sits at pos0[b] + t; a sequence whose start lies outside 0 .. L - T is
+// skipped -- its workgroups write neither q_out nor the caches (an idle slot of a serving loop).  The shared form trusts its caller.
+template <bool SEQ>
 __global__ __launch_bounds__(64) void rope_kv_prefill_kernel(const half_t* __restrict__ qkv, const half_t* __restrict__ cos_t,
                                                              const half_t* __restrict__ sin_t, const long* __restrict__ pos0,
                                                              half_t* __restrict__ q_out, half_t* __restrict__ k_cache,
                                                              half_t* __restrict__ v_cache, int T, int nh, int nkv, int D, int L) {
   const int bt = blockIdx.y, b = bt / T, t = bt % T, slot = blockIdx.x;
-  const long p = pos0[0] + t;
+  const long pb = pos0[SEQ ? b : 0];
+  if constexpr (SEQ) {
+    if (pb < 0 || pb > L - T) return;
+  }
+  const long p = pb + t;
   const half_t* src = qkv + (size_t)bt * (nh + 2 * nkv) * D + (size_t)slot * D;
   const int i = threadIdx.x;
   if (i >= D / 2) return;
@@ -253,7 +260,10 @@ __device__ __forceinline__ void rope8(const half8_t x, const half_t* __restrict_
 // that 256 positions are ONE trip -- one round of requests instead of two dependent ones -- and the first trip's requests no longer wait
 // for *pos: rows are clamped to the cache's end instead of to *pos - 1, and rows at or behind *pos are masked out of scores AND of the
 // value sum (their bytes may be anything).  Later trips clamp to *pos - 1 again (re-reading one row instead of fetching rows nobody needs).
-template <int WAVES, int UNR>
+// SEQ (all three fused kernels): pos holds one position per sequence and workgroup (b, .) uses pos[b] -- table row, append row and sweep
+// length are its own sequence's.  A sequence whose position lies outside 0 .. L - 1 is skipped: its workgroups leave before they write
+// the caches or out and before the barrier (the test is workgroup-uniform).  The shared forms (SEQ = false) are the kernels as they were.
+template <int WAVES, int UNR, bool SEQ>
 __global__ __launch_bounds__(WAVES * 64) void decode_rope_attention_flash_kernel(
     const half_t* __restrict__ qkv, const half_t* __restrict__ cos_t, const half_t* __restrict__ sin_t,
     const long* __restrict__ pos, half_t* __restrict__ k_cache, half_t* __restrict__ v_cache, half_t* __restrict__ out,
@@ -270,7 +280,8 @@ __global__ __launch_bounds__(WAVES * 64) void decode_rope_attention_flash_kernel
   const half8_t qraw = *(const half8_t*)(row + (size_t)h * D + sub * 8);
   const half8_t kraw = *(const half8_t*)(row + (size_t)(nh + kvh) * D + sub * 8);
   const half8_t vn = *(const half8_t*)(row + (size_t)(nh + nkv + kvh) * D + sub * 8);
-  const int p = (int)pos[0];  // cache rows 0..p-1 are attended from memory, row p (this token) from registers
+  const long pl = pos[SEQ ? b : 0];
+  const int p = (int)pl;  // cache rows 0..p-1 are attended from memory, row p (this token) from registers
   __builtin_amdgcn_sched_barrier(0);  // (the request for *pos leaves here, its wait sits behind the first trip's cache requests)
 
   const float LOG2E = 1.44269504088896f;
@@ -321,6 +332,9 @@ __global__ __launch_bounds__(WAVES * 64) void decode_rope_attention_flash_kernel
   int tb = uniform(wave * 4);
   request(kva, vva, tb, L - 1);
   __builtin_amdgcn_sched_barrier(0);  // (hipcc otherwise hoists the wait for *pos and the cos / sin rows in front of these requests)
+  if constexpr (SEQ) {
+    if (pl < 0 || pl >= L) return;  // a skipped sequence (the requests above are clamped to the cache's end: nobody waits for them)
+  }
   {  // rotate q and the new k while the cache rows are in flight
     #pragma clang fp contract(off)  // (each product rounded to fp16 on its own: hipcc would fuse one into a v_fma_f16 with the add)
     const half8_t cs = *(const half8_t*)(cos_t + (size_t)p * D + sub * 8), sn = *(const half8_t*)(sin_t + (size_t)p * D + sub * 8);
@@ -410,7 +424,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_rope_attention_flash_kernel
 // that KV head from ONE sweep over its K and V rows.  With one workgroup per query head every head of a group re-reads
 // the same cache rows through L2 and the launch is bound by that traffic, not by HBM: Mistral-7B shapes (32 query / 8 KV
 // heads) at bs=64, 190 positions took 33 us per layer for 50 MB of cache [r01, tools/time_attention.py].
-template <int GROUP, int UNR>
+template <int GROUP, int UNR, bool SEQ>
 __global__ __launch_bounds__(256, 2) void decode_rope_attention_gqa_kernel(
     const half_t* __restrict__ qkv, const half_t* __restrict__ cos_t, const half_t* __restrict__ sin_t,
     const long* __restrict__ pos, half_t* __restrict__ k_cache, half_t* __restrict__ v_cache, half_t* __restrict__ out,
@@ -429,7 +443,8 @@ __global__ __launch_bounds__(256, 2) void decode_rope_attention_gqa_kernel(
   for (int g = 0; g < GROUP; ++g) qraw[g] = *(const half8_t*)(row + (size_t)(hbase + g) * D + sub * 8);
   const half8_t kraw = *(const half8_t*)(row + (size_t)(nh + kvh) * D + sub * 8);
   const half8_t vn = *(const half8_t*)(row + (size_t)(nh + nkv + kvh) * D + sub * 8);
-  const int p = (int)pos[0];  // cache rows 0..p-1 are attended from memory, row p (this token) from registers
+  const long pl = pos[SEQ ? b : 0];
+  const int p = (int)pl;  // cache rows 0..p-1 are attended from memory, row p (this token) from registers
   __builtin_amdgcn_sched_barrier(0);  // (the request for *pos leaves here, its wait sits behind the first trip's cache requests)
 
   const float LOG2E = 1.44269504088896f;
@@ -445,6 +460,9 @@ __global__ __launch_bounds__(256, 2) void decode_rope_attention_gqa_kernel(
   // K and of V each), so that a wave always has cache rows in flight while it computes.  The one-set form (load a trip, wait, consume,
   // load the next) left the memory pipe empty during the arithmetic and the ALUs idle during the flight: 24.6 us per launch at bs = 64,
   // 8 KV heads, ~190 positions -- 50 MB, 2.0 TB/s (profiles/r05_decode_trace.txt).
+  if constexpr (SEQ) {
+    if (pl < 0 || pl >= L) return;  // a skipped sequence: nothing requested from the caches, nothing written
+  }
   const int plast = max(p - 1, 0);
   auto request = [&](half8_t (&kv)[UNR], half8_t (&vv)[UNR], int tb) __attribute__((always_inline)) {
     const int t0 = tb + rsel;
@@ -609,7 +627,7 @@ __device__ __forceinline__ float row_bcast(float x, int g) {   // the value of l
 #undef QA_BC
 }
 
-template <int GROUP, int UC>
+template <int GROUP, int UC, bool SEQ>
 __global__ __launch_bounds__(256, 2) void decode_rope_attention_gqa_mfma_kernel(
     const half_t* __restrict__ qkv, const half_t* __restrict__ cos_t, const half_t* __restrict__ sin_t,
     const long* __restrict__ pos, half_t* __restrict__ k_cache, half_t* __restrict__ v_cache, half_t* __restrict__ out,
@@ -648,7 +666,11 @@ __global__ __launch_bounds__(256, 2) void decode_rope_attention_gqa_mfma_kernel(
   half8_t kva[UC][4], vva[UC][4], kvb[UC][4], vvb[UC][4];
   constexpr int STEP = 64 * UC;
   int tb = wave * 16;   // first row of this wave's first chunk; a trip of the workgroup covers 64 UC rows
-  const int p = (int)pos[0];  // cache rows 0..p-1 come from memory, row p (this token) from registers
+  const long pl = pos[SEQ ? b : 0];
+  if constexpr (SEQ) {
+    if (pl < 0 || pl >= L) return;  // a skipped sequence: nothing requested from the caches, nothing written
+  }
+  const int p = (int)pl;  // cache rows 0..p-1 come from memory, row p (this token) from registers
   const int plast = max(p - 1, 0);
   // (requesting the first two sets before *pos is known -- rows clamped to the cache's end, masked afterwards -- measured no faster:
   // 16.4 against 15.2 us at bs = 64, 8 KV heads, 192 positions on two boxes, the same ratio to the vector-ALU sweep within 4 %)
@@ -1027,6 +1049,61 @@ static AttentionPick attention_pick(int batch, int n_heads, int n_kv_heads, int 
   return {AttentionPick::FLASH, 1, 1, pick == 8 ? 8 : 4};
 }
 
+template <bool SEQ>
+static int rope_kv_write_launch(const void* qkv, const void* cos_table, const void* sin_table, const void* pos0, void* q_out,
+                                void* k_cache, void* v_cache, int batch, int tokens, int n_heads, int n_kv_heads, int head_dim,
+                                int cache_len, void* hip_stream) {
+  if (batch <= 0 || tokens <= 0 || n_heads <= 0 || n_kv_heads <= 0 || head_dim % 2 != 0 || head_dim > 128 || n_heads % n_kv_heads != 0)
+    return QUICK_ERR_INVALID_ARGUMENT;
+  if ((long)batch * tokens > 65535) return QUICK_ERR_UNSUPPORTED;  // grid.y
+  hipLaunchKernelGGL(rope_kv_prefill_kernel<SEQ>, dim3(n_heads + 2 * n_kv_heads, batch * tokens), dim3(64), 0, (hipStream_t)hip_stream,
+                     (const half_t*)qkv, (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos0, (half_t*)q_out,
+                     (half_t*)k_cache, (half_t*)v_cache, tokens, n_heads, n_kv_heads, head_dim, cache_len);
+  return hipGetLastError() == hipSuccess ? QUICK_OK : QUICK_ERR_LAUNCH;
+}
+
+// SEQ = false: one position for the batch (*pos); true: pos[batch], one per sequence.  The same checks, the same pick, the same grid.
+template <bool SEQ>
+static int decode_rope_attention_launch(const void* qkv, const void* cos_table, const void* sin_table, const void* pos,
+                                        void* k_cache, void* v_cache, void* out, int batch, int n_heads, int n_kv_heads,
+                                        int head_dim, int cache_len, float scale, void* hip_stream) {
+  const int rc = attention_check(batch, n_heads, n_kv_heads, head_dim, cache_len);
+  if (rc != QUICK_OK) return rc;
+  const AttentionPick a = attention_pick(batch, n_heads, n_kv_heads, cache_len);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const dim3 grid_gqa(n_kv_heads * a.gsplit, batch);
+#define QA_GQA(GROUP)                                                                                                          \
+  hipLaunchKernelGGL((decode_rope_attention_gqa_kernel<GROUP, 4, SEQ>), grid_gqa, dim3(256), 0, st, (const half_t*)qkv,            \
+                     (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos, (half_t*)k_cache, (half_t*)v_cache, \
+                     (half_t*)out, n_heads, n_kv_heads, cache_len, scale, a.gsplit)
+#define QA_GQA_M(GROUP)                                                                                                        \
+  hipLaunchKernelGGL((decode_rope_attention_gqa_mfma_kernel<GROUP, 1, SEQ>), grid_gqa, dim3(256), 0, st, (const half_t*)qkv,       \
+                     (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos, (half_t*)k_cache, (half_t*)v_cache, \
+                     (half_t*)out, n_heads, n_kv_heads, cache_len, scale, a.gsplit)
+#define QA_FLASH(W)                                                                                                            \
+  hipLaunchKernelGGL((decode_rope_attention_flash_kernel<W, 4, SEQ>), dim3(n_heads, batch), dim3((W) * 64), 0, st,                 \
+                     (const half_t*)qkv, (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos,                 \
+                     (half_t*)k_cache, (half_t*)v_cache, (half_t*)out, n_heads, n_kv_heads, cache_len, scale)
+  switch (a.kind) {
+    case AttentionPick::GQA_MFMA:
+      if (a.heads == 8) QA_GQA_M(8);
+      else QA_GQA_M(4);
+      break;
+    case AttentionPick::GQA:
+      if (a.heads == 4) QA_GQA(4);
+      else QA_GQA(2);
+      break;
+    case AttentionPick::FLASH:
+      if (a.waves == 8) QA_FLASH(8);   // (two register sets of 4 rows per slot: the same 256 / 128 positions in flight as one set of 8)
+      else QA_FLASH(4);
+      break;
+  }
+#undef QA_GQA
+#undef QA_GQA_M
+#undef QA_FLASH
+  return hipGetLastError() == hipSuccess ? QUICK_OK : QUICK_ERR_LAUNCH;
+}
+
 }  // namespace quick_amd
 
 using namespace quick_amd;
@@ -1061,13 +1138,15 @@ int quick_rope_kv_append_f16(const void* qkv, const void* cos_table, const void*
 int quick_rope_kv_write_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos0, void* q_out,
                             void* k_cache, void* v_cache, int batch, int tokens, int n_heads, int n_kv_heads, int head_dim,
                             int cache_len, void* hip_stream) {
-  if (batch <= 0 || tokens <= 0 || n_heads <= 0 || n_kv_heads <= 0 || head_dim % 2 != 0 || head_dim > 128 || n_heads % n_kv_heads != 0)
-    return QUICK_ERR_INVALID_ARGUMENT;
-  if ((long)batch * tokens > 65535) return QUICK_ERR_UNSUPPORTED;  // grid.y
-  hipLaunchKernelGGL(rope_kv_prefill_kernel, dim3(n_heads + 2 * n_kv_heads, batch * tokens), dim3(64), 0, (hipStream_t)hip_stream,
-                     (const half_t*)qkv, (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos0, (half_t*)q_out,
-                     (half_t*)k_cache, (half_t*)v_cache, tokens, n_heads, n_kv_heads, head_dim, cache_len);
-  return hipGetLastError() == hipSuccess ? QUICK_OK : QUICK_ERR_LAUNCH;
+  return rope_kv_write_launch<false>(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, batch, tokens, n_heads, n_kv_heads,
+                                     head_dim, cache_len, hip_stream);
+}
+
+int quick_rope_kv_write_seq_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos0, void* q_out,
+                                void* k_cache, void* v_cache, int batch, int tokens, int n_heads, int n_kv_heads, int head_dim,
+                                int cache_len, void* hip_stream) {
+  return rope_kv_write_launch<true>(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, batch, tokens, n_heads, n_kv_heads,
+                                    head_dim, cache_len, hip_stream);
 }
 
 int quick_decode_attention_f16(const void* q, const void* k_cache, const void* v_cache, const void* pos, void* out,
@@ -1086,41 +1165,15 @@ int quick_decode_attention_f16(const void* q, const void* k_cache, const void* v
 int quick_decode_rope_attention_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos,
                                     void* k_cache, void* v_cache, void* out, int batch, int n_heads, int n_kv_heads,
                                     int head_dim, int cache_len, float scale, void* hip_stream) {
-  const int rc = attention_check(batch, n_heads, n_kv_heads, head_dim, cache_len);
-  if (rc != QUICK_OK) return rc;
-  const AttentionPick a = attention_pick(batch, n_heads, n_kv_heads, cache_len);
-  hipStream_t st = (hipStream_t)hip_stream;
-  const dim3 grid_gqa(n_kv_heads * a.gsplit, batch);
-#define QA_GQA(GROUP)                                                                                                          \
-  hipLaunchKernelGGL((decode_rope_attention_gqa_kernel<GROUP, 4>), grid_gqa, dim3(256), 0, st, (const half_t*)qkv,            \
-                     (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos, (half_t*)k_cache, (half_t*)v_cache, \
-                     (half_t*)out, n_heads, n_kv_heads, cache_len, scale, a.gsplit)
-#define QA_GQA_M(GROUP)                                                                                                        \
-  hipLaunchKernelGGL((decode_rope_attention_gqa_mfma_kernel<GROUP, 1>), grid_gqa, dim3(256), 0, st, (const half_t*)qkv,       \
-                     (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos, (half_t*)k_cache, (half_t*)v_cache, \
-                     (half_t*)out, n_heads, n_kv_heads, cache_len, scale, a.gsplit)
-#define QA_FLASH(W)                                                                                                            \
-  hipLaunchKernelGGL((decode_rope_attention_flash_kernel<W, 4>), dim3(n_heads, batch), dim3((W) * 64), 0, st,                 \
-                     (const half_t*)qkv, (const half_t*)cos_table, (const half_t*)sin_table, (const long*)pos,                 \
-                     (half_t*)k_cache, (half_t*)v_cache, (half_t*)out, n_heads, n_kv_heads, cache_len, scale)
-  switch (a.kind) {
-    case AttentionPick::GQA_MFMA:
-      if (a.heads == 8) QA_GQA_M(8);
-      else QA_GQA_M(4);
-      break;
-    case AttentionPick::GQA:
-      if (a.heads == 4) QA_GQA(4);
-      else QA_GQA(2);
-      break;
-    case AttentionPick::FLASH:
-      if (a.waves == 8) QA_FLASH(8);   // (two register sets of 4 rows per slot: the same 256 / 128 positions in flight as one set of 8)
-      else QA_FLASH(4);
-      break;
-  }
-#undef QA_GQA
-#undef QA_GQA_M
-#undef QA_FLASH
-  return hipGetLastError() == hipSuccess ? QUICK_OK : QUICK_ERR_LAUNCH;
+  return decode_rope_attention_launch<false>(qkv, cos_table, sin_table, pos, k_cache, v_cache, out, batch, n_heads, n_kv_heads,
+                                             head_dim, cache_len, scale, hip_stream);
+}
+
+int quick_decode_rope_attention_seq_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos,
+                                        void* k_cache, void* v_cache, void* out, int batch, int n_heads, int n_kv_heads,
+                                        int head_dim, int cache_len, float scale, void* hip_stream) {
+  return decode_rope_attention_launch<true>(qkv, cos_table, sin_table, pos, k_cache, v_cache, out, batch, n_heads, n_kv_heads,
+                                            head_dim, cache_len, scale, hip_stream);
 }
 
 int quick_decode_rope_attention_describe(int batch, int n_heads, int n_kv_heads, int head_dim, int cache_len, char* text,

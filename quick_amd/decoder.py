@@ -181,10 +181,14 @@ def decode_step_fused(model: SyntheticDecoder, tok, pos):
     -- 5 launches, 7 where the planner's kernel for the shape cannot take the RMSNorm prologue.  (Running the four GEMMs
     between two attention kernels as ONE persistent launch was built and measured in r02 and is slower than the four
     launches: profiles/r02_chain_experiment.txt.)  Same arithmetic as ``SyntheticDecoder.forward`` up to fp16 rounding
-    order.  Returns (next tokens [B], hidden [B, H])."""
+    order.  ``pos``: one device int64 for the whole batch, or B of them (B > 1) -- then sequence b sits at pos[b] and attention runs
+    its per-sequence launch.  Returns (next tokens [B], hidden [B, H])."""
     cfg = model.cfg
     nh, nkv, D, H, I, G = cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.hidden, cfg.intermediate, cfg.group_size
     B = tok.shape[0]
+    per_sequence = pos.numel() != 1
+    if per_sequence and pos.numel() != B:
+        raise ValueError(f"decode_step_fused: pos must hold 1 position or one per sequence ({B}), it holds {pos.numel()}")
     x = model.embed.index_select(0, tok.view(-1))                  # [B, H], a fresh buffer: the residual stream
     fuse_qkv = kernels.can_fuse_rmsnorm(B, H, H + 2 * nkv * D, G)
     fuse_gu = kernels.can_fuse_rmsnorm(B, H, 2 * I, G)
@@ -195,7 +199,10 @@ def decode_step_fused(model: SyntheticDecoder, tok, pos):
         else:
             kernels.rmsnorm(x, l["ln1"], out=model._h)
             _gemm(qkv, model._h, model._qkv)
-        kernels.rope_attention(model._qkv, model.cos, model.sin, pos, l["k"], l["v"], model._att, nh, nkv, D)
+        if per_sequence:
+            kernels.rope_attention(model._qkv, model.cos, model.sin, pos, l["k"], l["v"], model._att, nh, nkv, D, per_sequence=True)
+        else:
+            kernels.rope_attention(model._qkv, model.cos, model.sin, pos, l["k"], l["v"], model._att, nh, nkv, D)
         _gemm(l["o"], model._att, x, residual=x)                    # x += o_proj(att), added in the GEMM epilogue
         if fuse_gu:
             kernels.gemm_forward(x, gu.qweight, gu.scales, gu.qzeros, out=model._act, rmsnorm_weight=l["ln2"], silu_mul=True)

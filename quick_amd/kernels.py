@@ -483,9 +483,29 @@ def rope_kv_append(qkv, cos_table, sin_table, pos, q_out, k_cache, v_cache, n_he
     return q_out
 
 
-def rope_kv_write(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, tokens, n_heads, n_kv_heads, head_dim):
+def _per_sequence_pos(pos, batch, like, name):
+    """The position argument of a per-sequence launch: a device int64 tensor of exactly `batch` elements, on the device of `like`.
+    Anything else is a ValueError before the library is called (the kernels index it by the sequence)."""
+    if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int64:
+        raise ValueError(f"per_sequence: {name} must be an int64 tensor, got {getattr(pos, 'dtype', type(pos).__name__)}")
+    if pos.numel() != batch or not pos.is_contiguous():
+        raise ValueError(f"per_sequence: {name} must hold exactly one contiguous position per sequence ({batch}), it holds {pos.numel()}")
+    if not pos.is_cuda or pos.device != like.device:
+        raise ValueError(f"per_sequence: {name} must be a GPU tensor on the device of the caches ({like.device}), it is on {pos.device}")
+
+
+def rope_kv_write(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, tokens, n_heads, n_kv_heads, head_dim, per_sequence=False):
     """Prefill: qkv [B * T, (nh + 2 nkv) D] -> rotated q in q_out [B, nh, T, D], rotated k and v into the caches at
-    positions *pos0 .. *pos0 + T - 1."""
+    positions *pos0 .. *pos0 + T - 1.  ``per_sequence``: pos0 is a device int64 [B] and sequence b starts at pos0[b]
+    (quick_rope_kv_write_seq_f16); a sequence whose start lies outside 0 .. L - T is skipped."""
+    if per_sequence:
+        _per_sequence_pos(pos0, qkv.shape[0] // tokens, k_cache, "pos0")
+        rc = _lib.load().quick_rope_kv_write_seq_f16(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos0.data_ptr(),
+                                                     q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), qkv.shape[0] // tokens,
+                                                     tokens, n_heads, n_kv_heads, head_dim, k_cache.shape[2], _stream())
+        if rc != _OK:
+            raise RuntimeError(f"quick_rope_kv_write_seq_f16 failed ({rc})")
+        return q_out
     lib = _lib.load()
     rc = lib.quick_rope_kv_write_f16(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos0.data_ptr(), q_out.data_ptr(),
                                      k_cache.data_ptr(), v_cache.data_ptr(), qkv.shape[0] // tokens, tokens, n_heads, n_kv_heads,
@@ -495,12 +515,22 @@ def rope_kv_write(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, toke
     return q_out
 
 
-def prefill_attention(q, k_cache, v_cache, pos0, out, n_heads, n_kv_heads, head_dim):
+def prefill_attention(q, k_cache, v_cache, pos0, out, n_heads, n_kv_heads, head_dim, per_sequence=False):
     """Causal attention of T new tokens over the cache (quick_prefill_attention_f16): q [B, nh, T, D] as rope_kv_write leaves it, caches
     [B, nkv, L, D] with rows *pos0 .. *pos0 + T - 1 written, pos0 a device int64 -> out [B * T, nh * D] (row b * T + t).  Query t attends
-    cache rows 0 .. *pos0 + t; no host read, no mask tensor."""
+    cache rows 0 .. *pos0 + t; no host read, no mask tensor.  ``per_sequence``: pos0 is a device int64 [B] and query t of sequence b
+    attends rows 0 .. pos0[b] + t (quick_prefill_attention_seq_f16); a sequence whose start lies outside 0 .. L - T is skipped."""
+    if per_sequence:
+        _per_sequence_pos(pos0, q.shape[0], k_cache, "pos0")
     for t, name in ((q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (out, "out")):
         _expect(t, torch.float16, name)
+    if per_sequence:
+        rc = _lib.load().quick_prefill_attention_seq_f16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), pos0.data_ptr(),
+                                                         out.data_ptr(), q.shape[0], q.shape[2], n_heads, n_kv_heads, head_dim,
+                                                         k_cache.shape[2], head_dim ** -0.5, _stream())
+        if rc != _OK:
+            _raise(rc)
+        return out
     _expect(pos0, torch.int64, "pos0")
     lib = _lib.load()
     rc = lib.quick_prefill_attention_f16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), pos0.data_ptr(), out.data_ptr(),
@@ -530,8 +560,18 @@ def decode_attention(q, k_cache, v_cache, pos, out, n_heads, n_kv_heads, head_di
     return out
 
 
-def rope_attention(qkv, cos_table, sin_table, pos, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim):
-    """rope_kv_append + decode_attention in one launch: qkv [B, (nh + 2 nkv) D] -> out [B, nh * D]."""
+def rope_attention(qkv, cos_table, sin_table, pos, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, per_sequence=False):
+    """rope_kv_append + decode_attention in one launch: qkv [B, (nh + 2 nkv) D] -> out [B, nh * D].  ``per_sequence``: pos is a device
+    int64 [B]; sequence b rotates with table row pos[b], appends at cache row pos[b] and attends rows 0 .. pos[b]
+    (quick_decode_rope_attention_seq_f16); a sequence whose position lies outside 0 .. L - 1 is skipped."""
+    if per_sequence:
+        _per_sequence_pos(pos, qkv.shape[0], k_cache, "pos")
+        rc = _lib.load().quick_decode_rope_attention_seq_f16(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos.data_ptr(),
+                                                             k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), qkv.shape[0],
+                                                             n_heads, n_kv_heads, head_dim, k_cache.shape[2], head_dim ** -0.5, _stream())
+        if rc != _OK:
+            raise RuntimeError(f"quick_decode_rope_attention_seq_f16 failed ({rc})")
+        return out
     lib = _lib.load()
     rc = lib.quick_decode_rope_attention_f16(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos.data_ptr(),
                                              k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), qkv.shape[0], n_heads,

@@ -296,6 +296,55 @@ int quick_prefill_attention_seq_f16(const void* q, const void* k_cache, const vo
  * refusals as the launch (the pointers aside).  The wording may grow fields, the leading kernel word will not change. */
 int quick_prefill_attention_describe(int batch, int tokens, int n_heads, int n_kv_heads, int head_dim, int cache_len, char* text,
                                      size_t text_bytes);
+/*
+ * One-byte KV cache (opt-in; the fp16 entry points above are unchanged).  k_cache, v_cache: [batch, n_kv_heads, cache_len, 128], one byte
+ * per element, OCP e4m3fn (never the fnuz encoding).  One scale per cache, k_scale and v_scale: HOST floats, finite and > 0, constants
+ * of a captured graph.
+ *   stored byte        rne_e4m3(clamp(float(h) * inv, -448, 448)): h is the fp16 value the fp16 launch stores at that place (rotated K
+ *                      rounded to fp16 exactly as there, V copied), inv = 1.0f / scale computed once on the host in fp32.  The clamp is
+ *                      explicit (no conversion mode is relied on); NaN stays NaN (a NaN code).
+ *   dequantised value  float(byte) * scale.  The kernels fold the scales out of their sweeps: k_scale into the fp32 score factor
+ *                      scale * log2 e * k_scale, v_scale into the one fp32 multiply at the final division.  Inside the loops a byte
+ *                      becomes its exact fp16 value and nothing else; both MFMA products keep fp16 operands.
+ *   rows outside       rows at or behind a sequence's position may hold ANY byte (the NaN codes 0x7F / 0xFF included): they reach neither
+ *                      scores nor the value sum.
+ * per_sequence (the last int of each launch; one symbol serves both forms): 0 -- pos / pos0 is a DEVICE pointer to one int64 shared by
+ * the batch; non-zero -- to int64 [batch], with the skip rule of the _seq_f16 launches (a sequence whose position lies outside the valid
+ * range is left untouched: caches, q_out and out).
+ * Every entry point answers before any GPU work, with a sentence in quick_amd_last_error() -- shape rules first, then the scales, then
+ * the pointers:
+ *   quick_rope_kv_write_fp8           sizes <= 0, n_heads % n_kv_heads != 0                      QUICK_ERR_INVALID_ARGUMENT
+ *                                     head_dim != 128, batch * tokens > 65535                    QUICK_ERR_UNSUPPORTED
+ *   quick_decode_rope_attention_fp8   sizes <= 0, head_dim != 128, n_heads % n_kv_heads != 0,
+ *                                     a group other than 1, 2, 4, 8, batch > 65535              QUICK_ERR_UNSUPPORTED
+ *   quick_prefill_attention_fp8       sizes <= 0, tokens > cache_len                             QUICK_ERR_INVALID_ARGUMENT
+ *                                     head_dim != 128, n_heads % n_kv_heads != 0, grid limits    QUICK_ERR_UNSUPPORTED
+ *   all three                         a scale that is not finite and positive; a null pointer or one that is not 16-byte aligned
+ *                                     (pos / pos0: 8-byte)                                       QUICK_ERR_INVALID_ARGUMENT
+ * (the codes of the fp16 siblings, which accept other head dims in the write and do not look at pointers).
+ */
+/* quick_rope_kv_write_f16 for byte caches: RoPE on q and k of tokens >= 1 tokens per sequence; q_out [batch, n_heads, tokens, 128] in
+ * fp16, bit for bit what the fp16 launch writes; K and V rows stored as bytes in 8-byte pieces. */
+int quick_rope_kv_write_fp8(const void* qkv, const void* cos_table, const void* sin_table, const void* pos0, void* q_out, void* k_cache,
+                            void* v_cache, int batch, int tokens, int n_heads, int n_kv_heads, int head_dim, int cache_len, float k_scale,
+                            float v_scale, int per_sequence, void* hip_stream);
+/* quick_decode_rope_attention_f16 for byte caches: RoPE, append of the new token's K and V bytes at row *pos, single-query attention over
+ * rows 0 .. *pos.  1, 2, 4 or 8 query heads per KV head, a KV head's whole group served from ONE sweep of its rows (scores on
+ * v_mfma_f32_16x16x32_f16, 16 elements per 16-byte request, software-pipelined).  The new token takes part in its own step with its
+ * QUANTISED-then-dequantised K and V: step p attends exactly what step p + 1 reads from the cache. */
+int quick_decode_rope_attention_fp8(const void* qkv, const void* cos_table, const void* sin_table, const void* pos, void* k_cache,
+                                    void* v_cache, void* out, int batch, int n_heads, int n_kv_heads, int head_dim, int cache_len,
+                                    float scale, float k_scale, float v_scale, int per_sequence, void* hip_stream);
+/* The launch of quick_decode_rope_attention_fp8 for this shape as one line (host-only), e.g. "gqa-mfma-fp8 heads=4 gsplit=1 waves=4
+ * set_rows=64 grid=8x64": the build is chosen by the group alone.  The same shape refusals as the launch. */
+int quick_decode_rope_attention_fp8_describe(int batch, int n_heads, int n_kv_heads, int head_dim, int cache_len, char* text,
+                                             size_t text_bytes);
+/* quick_prefill_attention_f16 over byte caches: the same tiling, masking, online softmax, rounding points and way out; only the staging
+ * differs (half the bytes per request, converted to fp16 on the way into the same LDS images).  One build: no describe of its own,
+ * quick_prefill_attention_describe gives the grid. */
+int quick_prefill_attention_fp8(const void* q, const void* k_cache, const void* v_cache, const void* pos0, void* out, int batch, int tokens,
+                                int n_heads, int n_kv_heads, int head_dim, int cache_len, float scale, float k_scale, float v_scale,
+                                int per_sequence, void* hip_stream);
 int quick_silu_mul_f16(const void* gate_up, void* y, int rows, int intermediate, void* hip_stream);
 
 /* lm_head of a decode step with the greedy arg-max folded in (the reference: torch linear + max on the fp16 layer AWQ leaves

@@ -16,7 +16,13 @@ its cache, this module refuses: ``start_pos + T`` must not exceed ``max_seq_len`
 int64 [batch], ``forward(..., new_tokens=...)`` says how many of the T rows of each sequence are real (right-padded), and
 ``reset(slots=[...])`` frees single slots.  The launches are the per-sequence forms of the same kernels; each sequence's workgroups sweep
 its own length.  ``start_pos`` is then a host-side UPPER BOUND on the largest position, not the position.
+
+``kv_cache_dtype="fp8_e4m3"`` (opt-in, the default stays ``"fp16"``) keeps the caches in one byte per element, OCP e4m3fn, with one scale
+per cache: ``k_scale`` and ``v_scale``, host floats and constants of a captured graph.  ``quantize_kv`` / ``dequantize_kv`` below are the
+format, restated in torch: the kernels store ``quantize_kv`` of the fp16 rows the fp16 module would store and attend their
+``dequantize_kv`` -- the new token of a decode step included, so step p attends what step p + 1 reads.
 """
+import math
 import os
 
 import torch
@@ -25,12 +31,44 @@ import torch.nn as nn
 from . import kernels
 
 HEAD_DIM = 128
+KV_CACHE_DTYPES = {"fp16": torch.float16, "fp8_e4m3": torch.float8_e4m3fn}
+FP8_MAX = 448.0
+
+
+def _check_scale(scale, name):
+    scale = float(scale)
+    if not math.isfinite(scale) or scale <= 0.0:
+        raise ValueError(f"{name} must be finite and positive, got {scale}")
+    return scale
+
+
+def _check_kv_cache(who, kv_cache_dtype, k_scale, v_scale):
+    if kv_cache_dtype not in KV_CACHE_DTYPES:
+        raise ValueError(f"{who}: kv_cache_dtype must be one of {sorted(KV_CACHE_DTYPES)}, got {kv_cache_dtype!r}")
+    return KV_CACHE_DTYPES[kv_cache_dtype], _check_scale(k_scale, who + ": k_scale"), _check_scale(v_scale, who + ": v_scale")
+
+
+def quantize_kv(x, scale):
+    """The stored byte of the one-byte KV cache, as ``torch.float8_e4m3fn``: rne_e4m3(clamp(float(x) * inv, -448, 448)) with
+    inv = 1.0f / scale in fp32.  ``x`` is the fp16 value the fp16 cache would hold; CPU or GPU.  The clamp is explicit (+-448.0001 and
+    +-65504 saturate to +-448), ties go to the even code, NaN stays NaN."""
+    inv = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(_check_scale(scale, "scale"), dtype=torch.float32)   # one fp32 division
+    y = x.to(torch.float32) * inv.item()
+    return torch.clamp(y, -FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)   # (clamp lets NaN through)
+
+
+def dequantize_kv(b, scale):
+    """float32(byte) * scale: the value the kernels attend.  ``b`` is ``torch.float8_e4m3fn`` or a ``uint8`` view of the same bytes."""
+    if b.dtype == torch.uint8:
+        b = b.view(torch.float8_e4m3fn)
+    return b.to(torch.float32) * torch.tensor(_check_scale(scale, "scale"), dtype=torch.float32).item()
 
 
 class QuantAttentionFused(nn.Module):
     def __init__(self, hidden_size, n_heads, n_kv_heads, qkv_layer, o_proj, dev, max_seq_len, use_alibi=False, attention_shapes=None,
-                 rope_theta=10000, per_sequence=False):
+                 rope_theta=10000, per_sequence=False, kv_cache_dtype="fp16", k_scale=1.0, v_scale=1.0):
         super().__init__()
+        _, k_scale, v_scale = _check_kv_cache("QuantAttentionFused", kv_cache_dtype, k_scale, v_scale)
         if use_alibi:
             raise ValueError("QuantAttentionFused: use_alibi=True is not supported (the kernels rotate q and k, they add no ALiBi bias)")
         if attention_shapes is not None:
@@ -69,13 +107,14 @@ class QuantAttentionFused(nn.Module):
         self.cos = torch.cat((ang.cos(), ang.cos()), -1).half()
         self.sin = torch.cat((ang.sin(), ang.sin()), -1).half()
         self.per_sequence = bool(per_sequence)
+        self.kv_cache_dtype, self.k_scale, self.v_scale = kv_cache_dtype, k_scale, v_scale
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self._allocate(self.cache_batch_size, dev)
 
     def _allocate(self, batch, dev):
         shape = (batch, self.n_kv_heads, self.max_seq_len, HEAD_DIM)
-        self.k_cache = torch.zeros(shape, dtype=torch.float16, device=dev)
-        self.v_cache = torch.zeros(shape, dtype=torch.float16, device=dev)
+        self.k_cache = torch.zeros(shape, dtype=KV_CACHE_DTYPES[self.kv_cache_dtype], device=dev)
+        self.v_cache = torch.zeros(shape, dtype=KV_CACHE_DTYPES[self.kv_cache_dtype], device=dev)
         self.cache_batch_size = batch
         if self.per_sequence:                                   # one position per sequence, re-made with the caches
             self.pos = torch.zeros(batch, dtype=torch.int64, device=dev)
@@ -83,7 +122,11 @@ class QuantAttentionFused(nn.Module):
     def _apply(self, fn, *args, **kwargs):
         super()._apply(fn, *args, **kwargs)
         for name in ("cos", "sin", "k_cache", "v_cache"):       # (.to() / .cuda() move the state along with the projections)
-            setattr(self, name, fn(getattr(self, name)).half())
+            t = getattr(self, name)
+            if t.dtype == torch.float8_e4m3fn:                  # a byte cache moves as bytes: fn may be a dtype cast (.half())
+                setattr(self, name, fn(t.view(torch.uint8)).to(torch.uint8).view(torch.float8_e4m3fn))
+            else:
+                setattr(self, name, fn(t).half())
         self.pos = fn(self.pos).to(torch.int64)
         return self
 
@@ -156,15 +199,16 @@ class QuantAttentionFused(nn.Module):
         if not hidden_states.is_cuda:
             raise RuntimeError("hidden_states must be a GPU tensor: the attention kernels have no CPU implementation")
         nh, nkv = self.n_heads, self.n_kv_heads
+        ks = {} if self.kv_cache_dtype == "fp16" else dict(k_scale=self.k_scale, v_scale=self.v_scale)   # byte caches: the fp8 launches
         qkv = self.qkv_proj(hidden_states.reshape(B * T, self.hidden_size).contiguous())
         att = torch.empty((B * T, nh * HEAD_DIM), dtype=torch.float16, device=qkv.device)
         if self.per_sequence:
             if T == 1:
-                kernels.rope_attention(qkv, self.cos, self.sin, self.pos, self.k_cache, self.v_cache, att, nh, nkv, HEAD_DIM, per_sequence=True)
+                kernels.rope_attention(qkv, self.cos, self.sin, self.pos, self.k_cache, self.v_cache, att, nh, nkv, HEAD_DIM, per_sequence=True, **ks)
             else:
                 q = torch.empty((B, nh, T, HEAD_DIM), dtype=torch.float16, device=qkv.device)
-                kernels.rope_kv_write(qkv, self.cos, self.sin, self.pos, q, self.k_cache, self.v_cache, T, nh, nkv, HEAD_DIM, per_sequence=True)
-                kernels.prefill_attention(q, self.k_cache, self.v_cache, self.pos, att, nh, nkv, HEAD_DIM, per_sequence=True)
+                kernels.rope_kv_write(qkv, self.cos, self.sin, self.pos, q, self.k_cache, self.v_cache, T, nh, nkv, HEAD_DIM, per_sequence=True, **ks)
+                kernels.prefill_attention(q, self.k_cache, self.v_cache, self.pos, att, nh, nkv, HEAD_DIM, per_sequence=True, **ks)
             attn_output = self.o_proj(att).view(B, T, -1)
             if step is None:
                 self.pos.add_(T)
@@ -173,11 +217,11 @@ class QuantAttentionFused(nn.Module):
             self.start_pos += advance
             return attn_output, att.view(B, T, nh * HEAD_DIM), [torch.zeros(1, 1, self.start_pos, 1)]
         if T == 1:
-            kernels.rope_attention(qkv, self.cos, self.sin, self.pos, self.k_cache, self.v_cache, att, nh, nkv, HEAD_DIM)
+            kernels.rope_attention(qkv, self.cos, self.sin, self.pos, self.k_cache, self.v_cache, att, nh, nkv, HEAD_DIM, **ks)
         else:
             q = torch.empty((B, nh, T, HEAD_DIM), dtype=torch.float16, device=qkv.device)
-            kernels.rope_kv_write(qkv, self.cos, self.sin, self.pos, q, self.k_cache, self.v_cache, T, nh, nkv, HEAD_DIM)
-            kernels.prefill_attention(q, self.k_cache, self.v_cache, self.pos, att, nh, nkv, HEAD_DIM)
+            kernels.rope_kv_write(qkv, self.cos, self.sin, self.pos, q, self.k_cache, self.v_cache, T, nh, nkv, HEAD_DIM, **ks)
+            kernels.prefill_attention(q, self.k_cache, self.v_cache, self.pos, att, nh, nkv, HEAD_DIM, **ks)
         attn_output = self.o_proj(att).view(B, T, -1)
         self.pos.add_(T)
         self.start_pos += T

@@ -70,7 +70,12 @@ def _rope(x, cos, sin):
 
 
 class SyntheticDecoder:
-    def __init__(self, cfg: DecoderConfig, batch, max_len, device, seed=0):
+    def __init__(self, cfg: DecoderConfig, batch, max_len, device, seed=0, kv_cache_dtype="fp16", k_scale=1.0, v_scale=1.0):
+        """``kv_cache_dtype="fp8_e4m3"``: one-byte caches (quick_amd.attention.quantize_kv with ``k_scale`` / ``v_scale``), served by
+        ``decode_step_fused`` and by ``forward(hip_glue=True, hip_attention=True, mask=None)``; the eager paths of ``forward`` need fp16."""
+        from .attention import _check_kv_cache
+        cache_dtype, self.k_scale, self.v_scale = _check_kv_cache("SyntheticDecoder", kv_cache_dtype, k_scale, v_scale)
+        self.kv_cache_dtype = kv_cache_dtype
         self.cfg, self.B, self.max_len, self.dev = cfg, batch, max_len, device
         g = torch.Generator(device=device).manual_seed(seed)
         H, KV, D, I, G = cfg.hidden, cfg.kv_heads * cfg.head_dim, cfg.head_dim, cfg.intermediate, cfg.group_size
@@ -80,8 +85,8 @@ class SyntheticDecoder:
                 qkv=random_wqlinear(H, H + 2 * KV, G, device, g), o=random_wqlinear(H, H, G, device, g),
                 gate_up=random_wqlinear(H, 2 * I, G, device, g), down=random_wqlinear(I, H, G, device, g),
                 ln1=torch.ones(H, dtype=torch.float16, device=device), ln2=torch.ones(H, dtype=torch.float16, device=device),
-                k=torch.zeros(batch, cfg.kv_heads, max_len, D, dtype=torch.float16, device=device),
-                v=torch.zeros(batch, cfg.kv_heads, max_len, D, dtype=torch.float16, device=device)))
+                k=torch.zeros(batch, cfg.kv_heads, max_len, D, dtype=cache_dtype, device=device),
+                v=torch.zeros(batch, cfg.kv_heads, max_len, D, dtype=cache_dtype, device=device)))
         self.embed = (torch.randn(cfg.vocab, H, device=device, generator=g) * 0.02).half()
         self.lm_head = (torch.randn(cfg.vocab, H, device=device, generator=g) * 0.02).half()
         self.norm = torch.ones(H, dtype=torch.float16, device=device)
@@ -118,16 +123,20 @@ class SyntheticDecoder:
         cos, sin = self.cos.index_select(0, pos), self.sin.index_select(0, pos)
         norm = (lambda v, w: kernels.rmsnorm(v.reshape(-1, H), w).view(v.shape)) if hip_glue else _rms_norm
         hip_attention = hip_attention and hip_glue and mask is None
+        if self.kv_cache_dtype != "fp16" and (not hip_attention or B * T > 65535):
+            raise ValueError("SyntheticDecoder.forward: a one-byte KV cache needs hip_glue=True, hip_attention=True, mask=None and "
+                             "B * T <= 65535 (the eager paths write and read fp16 caches)")
+        ks = dict(k_scale=self.k_scale, v_scale=self.v_scale)
         p0 = int(pos[0]) if (hip_glue and mask is None and not hip_attention) else 0   # one host read per prefill, not per layer
         for l in self.layers:
             h = norm(x, l["ln1"])
             qkv = l["qkv"](h)                                          # W4A16 GEMM, M = B*T
             if hip_glue and mask is None and B * T <= 65535:           # prefill: RoPE + cache write in one launch
                 q = torch.empty((B, nh, T, D), dtype=torch.float16, device=x.device)
-                kernels.rope_kv_write(qkv.reshape(B * T, -1), self.cos, self.sin, pos[:1], q, l["k"], l["v"], T, nh, nkv, D)
+                kernels.rope_kv_write(qkv.reshape(B * T, -1), self.cos, self.sin, pos[:1], q, l["k"], l["v"], T, nh, nkv, D, **ks)
                 if hip_attention:                                      # causal over cache rows 0 .. pos[0] + t, rows [B * T, H] as o wants them
                     att = torch.empty((B * T, H), dtype=torch.float16, device=x.device)
-                    kernels.prefill_attention(q, l["k"], l["v"], pos[:1], att, nh, nkv, D)
+                    kernels.prefill_attention(q, l["k"], l["v"], pos[:1], att, nh, nkv, D, **ks)
                 else:
                     att = F.scaled_dot_product_attention(q, l["k"][:, :, p0:p0 + T], l["v"][:, :, p0:p0 + T], is_causal=True,
                                                          enable_gqa=nkv != nh)
@@ -199,7 +208,10 @@ def decode_step_fused(model: SyntheticDecoder, tok, pos):
         else:
             kernels.rmsnorm(x, l["ln1"], out=model._h)
             _gemm(qkv, model._h, model._qkv)
-        if per_sequence:
+        if model.kv_cache_dtype != "fp16":                        # one-byte caches: the fp8 launch, either position form
+            kernels.rope_attention(model._qkv, model.cos, model.sin, pos, l["k"], l["v"], model._att, nh, nkv, D, per_sequence=per_sequence,
+                                   k_scale=model.k_scale, v_scale=model.v_scale)
+        elif per_sequence:
             kernels.rope_attention(model._qkv, model.cos, model.sin, pos, l["k"], l["v"], model._att, nh, nkv, D, per_sequence=True)
         else:
             kernels.rope_attention(model._qkv, model.cos, model.sin, pos, l["k"], l["v"], model._att, nh, nkv, D)

@@ -494,10 +494,39 @@ def _per_sequence_pos(pos, batch, like, name):
         raise ValueError(f"per_sequence: {name} must be a GPU tensor on the device of the caches ({like.device}), it is on {pos.device}")
 
 
-def rope_kv_write(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, tokens, n_heads, n_kv_heads, head_dim, per_sequence=False):
+_BYTE_DTYPES = (torch.float8_e4m3fn, torch.uint8)
+
+
+def _byte_caches(k_cache, v_cache):
+    """True when the caches are one-byte (OCP e4m3fn; a uint8 view of the same bytes is accepted): the launch is then the fp8 one.  A
+    pair of unequal kinds is a RuntimeError; fp16 caches (False) take the path they always took."""
+    kb, vb = k_cache.dtype in _BYTE_DTYPES, v_cache.dtype in _BYTE_DTYPES
+    if kb != vb:
+        raise RuntimeError(f"k_cache and v_cache must be of one kind, got {k_cache.dtype} and {v_cache.dtype}")
+    if kb:
+        for t, name in ((k_cache, "k_cache"), (v_cache, "v_cache")):
+            if not t.is_cuda or not t.is_contiguous() or t.dim() != 4:
+                raise RuntimeError(f"{name} must be a contiguous 4-D GPU tensor [batch, n_kv_heads, cache_len, head_dim]")
+    return kb
+
+
+def rope_kv_write(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, tokens, n_heads, n_kv_heads, head_dim, per_sequence=False,
+                  k_scale=1.0, v_scale=1.0):
     """Prefill: qkv [B * T, (nh + 2 nkv) D] -> rotated q in q_out [B, nh, T, D], rotated k and v into the caches at
     positions *pos0 .. *pos0 + T - 1.  ``per_sequence``: pos0 is a device int64 [B] and sequence b starts at pos0[b]
-    (quick_rope_kv_write_seq_f16); a sequence whose start lies outside 0 .. L - T is skipped."""
+    (quick_rope_kv_write_seq_f16); a sequence whose start lies outside 0 .. L - T is skipped.  One-byte caches
+    (``torch.float8_e4m3fn``, or ``uint8`` holding the same bytes) are written by quick_rope_kv_write_fp8 as
+    ``attention.quantize_kv`` of the rows the fp16 launch would store, with ``k_scale`` / ``v_scale``; q_out is the same, bit for bit."""
+    if _byte_caches(k_cache, v_cache):
+        if per_sequence:
+            _per_sequence_pos(pos0, qkv.shape[0] // tokens, k_cache, "pos0")
+        rc = _lib.load().quick_rope_kv_write_fp8(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos0.data_ptr(),
+                                                 q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), qkv.shape[0] // tokens, tokens,
+                                                 n_heads, n_kv_heads, head_dim, k_cache.shape[2], k_scale, v_scale, int(per_sequence),
+                                                 _stream())
+        if rc != _OK:
+            _raise(rc)
+        return q_out
     if per_sequence:
         _per_sequence_pos(pos0, qkv.shape[0] // tokens, k_cache, "pos0")
         rc = _lib.load().quick_rope_kv_write_seq_f16(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos0.data_ptr(),
@@ -515,13 +544,24 @@ def rope_kv_write(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, toke
     return q_out
 
 
-def prefill_attention(q, k_cache, v_cache, pos0, out, n_heads, n_kv_heads, head_dim, per_sequence=False):
+def prefill_attention(q, k_cache, v_cache, pos0, out, n_heads, n_kv_heads, head_dim, per_sequence=False, k_scale=1.0, v_scale=1.0):
     """Causal attention of T new tokens over the cache (quick_prefill_attention_f16): q [B, nh, T, D] as rope_kv_write leaves it, caches
     [B, nkv, L, D] with rows *pos0 .. *pos0 + T - 1 written, pos0 a device int64 -> out [B * T, nh * D] (row b * T + t).  Query t attends
     cache rows 0 .. *pos0 + t; no host read, no mask tensor.  ``per_sequence``: pos0 is a device int64 [B] and query t of sequence b
-    attends rows 0 .. pos0[b] + t (quick_prefill_attention_seq_f16); a sequence whose start lies outside 0 .. L - T is skipped."""
+    attends rows 0 .. pos0[b] + t (quick_prefill_attention_seq_f16); a sequence whose start lies outside 0 .. L - T is skipped.
+    One-byte caches run quick_prefill_attention_fp8 with ``k_scale`` / ``v_scale`` (see rope_kv_write)."""
     if per_sequence:
         _per_sequence_pos(pos0, q.shape[0], k_cache, "pos0")
+    if _byte_caches(k_cache, v_cache):
+        for t, name in ((q, "q"), (out, "out")):
+            _expect(t, torch.float16, name)
+        _expect(pos0, torch.int64, "pos0")
+        rc = _lib.load().quick_prefill_attention_fp8(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), pos0.data_ptr(), out.data_ptr(),
+                                                     q.shape[0], q.shape[2], n_heads, n_kv_heads, head_dim, k_cache.shape[2],
+                                                     head_dim ** -0.5, k_scale, v_scale, int(per_sequence), _stream())
+        if rc != _OK:
+            _raise(rc)
+        return out
     for t, name in ((q, "q"), (k_cache, "k_cache"), (v_cache, "v_cache"), (out, "out")):
         _expect(t, torch.float16, name)
     if per_sequence:
@@ -560,10 +600,22 @@ def decode_attention(q, k_cache, v_cache, pos, out, n_heads, n_kv_heads, head_di
     return out
 
 
-def rope_attention(qkv, cos_table, sin_table, pos, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, per_sequence=False):
+def rope_attention(qkv, cos_table, sin_table, pos, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, per_sequence=False,
+                   k_scale=1.0, v_scale=1.0):
     """rope_kv_append + decode_attention in one launch: qkv [B, (nh + 2 nkv) D] -> out [B, nh * D].  ``per_sequence``: pos is a device
     int64 [B]; sequence b rotates with table row pos[b], appends at cache row pos[b] and attends rows 0 .. pos[b]
-    (quick_decode_rope_attention_seq_f16); a sequence whose position lies outside 0 .. L - 1 is skipped."""
+    (quick_decode_rope_attention_seq_f16); a sequence whose position lies outside 0 .. L - 1 is skipped.  One-byte caches run
+    quick_decode_rope_attention_fp8 with ``k_scale`` / ``v_scale``: the new token is appended as bytes and attended in that form."""
+    if _byte_caches(k_cache, v_cache):
+        if per_sequence:
+            _per_sequence_pos(pos, qkv.shape[0], k_cache, "pos")
+        rc = _lib.load().quick_decode_rope_attention_fp8(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos.data_ptr(),
+                                                         k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), qkv.shape[0], n_heads,
+                                                         n_kv_heads, head_dim, k_cache.shape[2], head_dim ** -0.5, k_scale, v_scale,
+                                                         int(per_sequence), _stream())
+        if rc != _OK:
+            _raise(rc)
+        return out
     if per_sequence:
         _per_sequence_pos(pos, qkv.shape[0], k_cache, "pos")
         rc = _lib.load().quick_decode_rope_attention_seq_f16(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos.data_ptr(),
@@ -581,10 +633,14 @@ def rope_attention(qkv, cos_table, sin_table, pos, k_cache, v_cache, out, n_head
     return out
 
 
-def attention_describe(batch, n_heads, n_kv_heads, head_dim, cache_len):
-    """One line saying which kernel rope_attention runs for this shape (quick_decode_rope_attention_describe; host-only, no GPU needed)."""
+def attention_describe(batch, n_heads, n_kv_heads, head_dim, cache_len, kv_cache_dtype="fp16"):
+    """One line saying which kernel rope_attention runs for this shape (quick_decode_rope_attention_describe; host-only, no GPU needed).
+    ``kv_cache_dtype="fp8_e4m3"``: the launch over one-byte caches (quick_decode_rope_attention_fp8_describe)."""
+    if kv_cache_dtype not in ("fp16", "fp8_e4m3"):
+        raise ValueError(f"attention_describe: kv_cache_dtype must be 'fp16' or 'fp8_e4m3', got {kv_cache_dtype!r}")
     buf = ctypes.create_string_buffer(128)
-    rc = _lib.load().quick_decode_rope_attention_describe(batch, n_heads, n_kv_heads, head_dim, cache_len, buf, len(buf))
+    fn = _lib.load().quick_decode_rope_attention_fp8_describe if kv_cache_dtype == "fp8_e4m3" else _lib.load().quick_decode_rope_attention_describe
+    rc = fn(batch, n_heads, n_kv_heads, head_dim, cache_len, buf, len(buf))
     if rc != _OK:
         _raise(rc)
     return buf.value.decode()

@@ -345,6 +345,60 @@ int quick_decode_rope_attention_fp8_describe(int batch, int n_heads, int n_kv_he
 int quick_prefill_attention_fp8(const void* q, const void* k_cache, const void* v_cache, const void* pos0, void* out, int batch, int tokens,
                                 int n_heads, int n_kv_heads, int head_dim, int cache_len, float scale, float k_scale, float v_scale,
                                 int per_sequence, void* hip_stream);
+/*
+ * Sliding-window attention over a RING KV cache, fp16 (opt-in; every entry point above is unchanged).  The query at position p attends
+ * positions max(0, p - window + 1) .. p.  k_cache, v_cache: [batch, n_kv_heads, ring_rows, 128] fp16; position j lives in cache row
+ * j % ring_rows, so cache memory and the decode sweep are bounded by the window, not by the context.  Keys keep the RoPE of their own
+ * ABSOLUTE position: nothing is re-labelled when the window moves.
+ *   R = ring_rows   rows of the cache tensors
+ *   W = window      W <= R
+ *   table_rows      rows of the cos / sin tables: the exclusive bound on positions
+ * Ring rule.  A chunk of T tokens is written before it is attended and overwrites the rows of positions <= pos0 + T - 1 - R.  With
+ * W + T - 1 <= R the oldest position any query of the chunk attends, pos0 - W + 1, lies in front of that: no attended row has been
+ * overwritten.  A ring that can never wrap, R >= table_rows, takes any T <= R.
+ * Never read.  Every cache row that holds no position inside [window start of the launch's first query, last written position] -- rows
+ * not yet written before the first wrap, stale rows of positions in front of the window after it -- may hold anything, NaN keys and
+ * +-Inf values included.  Positions inside that span but outside a given query's own window are requested (they are finite) and masked
+ * by the row index before the max and the exp, as the causal diagonal is.  The prefill launch never writes a cache; the decode launch
+ * writes row *pos % R and nothing else.
+ * Rounding points: those of quick_decode_rope_attention_f16's grouped MFMA sweep (fp32 scores, max, sum and P V; one division and one
+ * rounding at the end) and of quick_prefill_attention_f16 (P rounded to fp16 as the operand of the second product).
+ * per_sequence, as in the fp8 launches: 0 -- pos / pos0 is a DEVICE pointer to one int64 shared by the batch (a value outside the valid
+ * range is pulled inside); non-zero -- to int64 [batch], and a sequence whose position lies outside the valid range is skipped and left
+ * untouched: caches, q_out and out.  Valid: pos0 in 0 .. table_rows - tokens, *pos in 0 .. table_rows - 1.
+ * The prefill launch and the describe take table_rows too: the ring rule and the skip rule cannot be stated without it.
+ * Every entry point answers before any GPU work, with a sentence in quick_amd_last_error(), in this order:
+ *   a size <= 0, window < 1, window > ring_rows, tokens > ring_rows, tokens > table_rows                 QUICK_ERR_INVALID_ARGUMENT
+ *   window + tokens - 1 > ring_rows while ring_rows < table_rows (attention launches and the describe)    QUICK_ERR_INVALID_ARGUMENT
+ *   head_dim != 128, n_heads % n_kv_heads != 0, decode: a group other than 1, 2, 4, 8                     QUICK_ERR_UNSUPPORTED
+ *   a grid limit (write: batch * tokens > 65535; attention: batch or n_heads > 65535)                     QUICK_ERR_UNSUPPORTED
+ *   a null pointer                                                                                        QUICK_ERR_INVALID_ARGUMENT
+ */
+/* quick_rope_kv_write_f16 into the ring: token t is rotated with table row pos0 + t and its K and V are stored at cache row
+ * (pos0 + t) % ring_rows.  q_out and the stored rows are bit for bit what quick_rope_kv_write_f16 writes (at row pos0 + t of a linear
+ * cache) for the same qkv and position. */
+int quick_rope_kv_write_win_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos0, void* q_out, void* k_cache,
+                                void* v_cache, int batch, int tokens, int n_heads, int n_kv_heads, int head_dim, int ring_rows,
+                                int table_rows, int per_sequence, void* hip_stream);
+/* One launch: RoPE at *pos, append at cache row *pos % ring_rows, single-query attention over positions max(0, *pos - window + 1) ..
+ * *pos; the new token comes from registers.  1, 2, 4 or 8 query heads per KV head, a KV head's whole group served from ONE sweep with
+ * the scores on v_mfma_f32_16x16x32_f16.  The sweep runs over logical positions: the window start is reduced modulo ring_rows once per
+ * workgroup, every further row is a compare and a subtract. */
+int quick_decode_rope_attention_win_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos, void* k_cache,
+                                        void* v_cache, void* out, int batch, int n_heads, int n_kv_heads, int head_dim, int ring_rows,
+                                        int window, int table_rows, float scale, int per_sequence, void* hip_stream);
+/* quick_prefill_attention_f16 with a window over the ring: query t attends positions max(0, pos0 + t - window + 1) .. pos0 + t, whose
+ * rows quick_rope_kv_write_win_f16 has written.  Tiling, LDS images, online softmax, rounding points and the way out are that kernel's;
+ * a workgroup starts at the tile that holds the window start of its first query, and the lower diagonal is masked like the upper one.
+ * out: [batch * tokens, n_heads * 128]. */
+int quick_prefill_attention_win_f16(const void* q, const void* k_cache, const void* v_cache, const void* pos0, void* out, int batch,
+                                    int tokens, int n_heads, int n_kv_heads, int head_dim, int ring_rows, int window, int table_rows,
+                                    float scale, int per_sequence, void* hip_stream);
+/* The windowed attention launch for this shape as one line (host-only): tokens == 1 describes the decode launch ("decode-win-mfma
+ * heads=4 waves=4 set_rows=64 ring_rows=4607 window=4096 grid=8x64"), more tokens the prefill launch ("prefill-win-mfma q_rows=64
+ * kv_rows=32 waves=4 ...").  The same shape refusals as the launches. */
+int quick_attention_win_describe(int batch, int tokens, int n_heads, int n_kv_heads, int head_dim, int ring_rows, int window,
+                                 int table_rows, char* text, size_t text_bytes);
 int quick_silu_mul_f16(const void* gate_up, void* y, int rows, int intermediate, void* hip_stream);
 
 /* lm_head of a decode step with the greedy arg-max folded in (the reference: torch linear + max on the fp16 layer AWQ leaves

@@ -42,6 +42,10 @@ _SIGNATURES = {
     "quick_decode_rope_attention_fp8": (_I, [_P] * 7 + [_I] * 5 + [ctypes.c_float] * 3 + [_I, _P]),
     "quick_decode_rope_attention_fp8_describe": (_I, [_I] * 5 + [ctypes.c_char_p, _Z]),
     "quick_prefill_attention_fp8": (_I, [_P] * 5 + [_I] * 6 + [ctypes.c_float] * 3 + [_I, _P]),
+    "quick_rope_kv_write_win_f16": (_I, [_P] * 7 + [_I] * 8 + [_P]),
+    "quick_decode_rope_attention_win_f16": (_I, [_P] * 7 + [_I] * 7 + [ctypes.c_float, _I, _P]),
+    "quick_prefill_attention_win_f16": (_I, [_P] * 5 + [_I] * 8 + [ctypes.c_float, _I, _P]),
+    "quick_attention_win_describe": (_I, [_I] * 8 + [ctypes.c_char_p, _Z]),
     "quick_silu_mul_f16": (_I, [_P, _P, _I, _I, _P]),
     "quick_lm_head_workspace_bytes": (_Z, [_I]),
     "quick_lm_head_argmax_f16": (_I, [_P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _P]),

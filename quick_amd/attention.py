@@ -10,7 +10,14 @@ the device (``start_pos`` mirrors it on the host), so a forward can be captured 
 non-empty cache (second chat turn, chunked prefill, speculative verify) attends the whole cache.
 
 Envelope: inference, fp16, head_dim 128, rotate-half RoPE (HF convention, the reference's ``is_neox=True``).  Where the reference rolls
-its cache, this module refuses: ``start_pos + T`` must not exceed ``max_seq_len``.
+its cache, this module refuses: ``start_pos + T`` must not exceed ``max_seq_len`` -- the rows of the RoPE tables.
+
+``sliding_window=W`` (opt-in; fp16 caches) makes the attention banded: the query at position p attends positions max(0, p - W + 1) .. p,
+and the caches become RINGS of ``ring_rows(W, prefill_chunk, max_seq_len)`` rows in which position j lives in row ``ring_slot(j, rows)``.
+Cache memory and the decode sweep are then bounded by the window, not by the context.  Keys keep the RoPE of their own absolute position
+(the reference's ``roll_kv_n_steps`` shifts ``start_pos`` and so re-labels the cached keys; that is not copied).  A prompt goes in
+chunks of at most ``prefill_chunk`` tokens: a chunk is written before it is attended, and with W + T - 1 <= rows the rows it
+overwrites hold positions in front of every window of the chunk.  ``window_attention_reference`` restates the result in float64.
 
 ``per_sequence=True`` (a keyword of this package, not of the reference) gives every sequence of the batch its own position: ``pos`` is
 int64 [batch], ``forward(..., new_tokens=...)`` says how many of the T rows of each sequence are real (right-padded), and
@@ -64,11 +71,67 @@ def dequantize_kv(b, scale):
     return b.to(torch.float32) * torch.tensor(_check_scale(scale, "scale"), dtype=torch.float32).item()
 
 
+def ring_rows(window, prefill_chunk, max_seq_len):
+    """Rows of the ring caches of a sliding window: min(max_seq_len, window + prefill_chunk - 1).  window + T - 1 rows let a chunk of
+    T <= prefill_chunk tokens be written before it is attended without overwriting a row it attends; max_seq_len rows never wrap."""
+    window, prefill_chunk, max_seq_len = int(window), int(prefill_chunk), int(max_seq_len)
+    if window < 1 or prefill_chunk < 1 or max_seq_len < 1:
+        raise ValueError(f"ring_rows: window, prefill_chunk and max_seq_len must be at least 1, got {window}, {prefill_chunk}, {max_seq_len}")
+    return min(max_seq_len, window + prefill_chunk - 1)
+
+
+def ring_slot(pos, ring_rows):
+    """The cache row of position ``pos`` (an int, or an integer tensor of positions) in a ring of ``ring_rows`` rows: pos % ring_rows."""
+    if int(ring_rows) < 1:
+        raise ValueError(f"ring_slot: ring_rows must be at least 1, got {ring_rows}")
+    return pos % int(ring_rows)
+
+
+def window_attention_reference(q, k_ring, v_ring, pos0, window):
+    """float64 banded-causal softmax(q K^T / sqrt(D)) V, the restatement of the windowed launches: q [B, nh, T, D] (rotated, as
+    rope_kv_write leaves it), ring caches [B, nkv, R, D] in which position j lives in row ring_slot(j, R) and positions
+    max(0, pos0 - window + 1) .. pos0 + T - 1 are present, pos0 an int or one int per sequence.  Query t attends positions
+    max(0, pos0 + t - window + 1) .. pos0 + t: those rows are gathered out of the ring, and no other row is looked at.  Returns the
+    kernels' row order, [B * T, nh * D], in float64.  CPU or GPU tensors."""
+    B, nh, T, Dh = q.shape
+    nkv, R = k_ring.shape[1], k_ring.shape[2]
+    window = int(window)
+    if window < 1 or nh % nkv != 0:
+        raise ValueError("window_attention_reference: window must be at least 1 and n_heads a multiple of n_kv_heads")
+    starts = [int(pos0)] * B if not isinstance(pos0, (list, tuple, torch.Tensor)) else [int(p) for p in pos0]
+    if len(starts) != B or min(starts) < 0:
+        raise ValueError(f"window_attention_reference: pos0 must be one non-negative position, or one per sequence ({B})")
+    out = torch.empty((B, T, nh, Dh), dtype=torch.float64, device=q.device)
+    scale = Dh ** -0.5
+    for b, p0 in enumerate(starts):
+        lo = max(0, p0 - window + 1)
+        if p0 + T - lo > R:
+            raise ValueError(f"window_attention_reference: positions {lo} .. {p0 + T - 1} do not fit a ring of {R} rows")
+        span = torch.arange(lo, p0 + T, device=q.device)                                       # the positions any query of b attends
+        K = k_ring[b][:, ring_slot(span, R)].double()                                          # [nkv, n, D]
+        V = v_ring[b][:, ring_slot(span, R)].double()
+        qp = p0 + torch.arange(T, device=q.device)[:, None]
+        vis = (span[None, :] <= qp) & (span[None, :] > qp - window)                            # [T, n]
+        s = torch.einsum("kgtd,knd->kgtn", q[b].double().view(nkv, nh // nkv, T, Dh), K) * scale
+        P = torch.softmax(torch.where(vis, s, torch.full_like(s, float("-inf"))), -1)
+        P = torch.where(vis, P, torch.zeros_like(P))                                           # (an exact 0: 0 * V stays 0)
+        out[b] = torch.einsum("kgtn,knd->kgtd", P, V).reshape(nh, T, Dh).transpose(0, 1)
+    return out.reshape(B * T, nh * Dh)
+
+
 class QuantAttentionFused(nn.Module):
     def __init__(self, hidden_size, n_heads, n_kv_heads, qkv_layer, o_proj, dev, max_seq_len, use_alibi=False, attention_shapes=None,
-                 rope_theta=10000, per_sequence=False, kv_cache_dtype="fp16", k_scale=1.0, v_scale=1.0):
+                 rope_theta=10000, per_sequence=False, kv_cache_dtype="fp16", k_scale=1.0, v_scale=1.0, sliding_window=None,
+                 prefill_chunk=512):
         super().__init__()
         _, k_scale, v_scale = _check_kv_cache("QuantAttentionFused", kv_cache_dtype, k_scale, v_scale)
+        if prefill_chunk is None or int(prefill_chunk) != prefill_chunk or prefill_chunk < 1:
+            raise ValueError(f"QuantAttentionFused: prefill_chunk must be a whole number >= 1, got {prefill_chunk!r}")
+        if sliding_window is not None:
+            if int(sliding_window) != sliding_window or sliding_window < 1:
+                raise ValueError(f"QuantAttentionFused: sliding_window must be a whole number >= 1 (or None), got {sliding_window!r}")
+            if kv_cache_dtype != "fp16":
+                raise ValueError("QuantAttentionFused: sliding_window needs kv_cache_dtype='fp16' (a window over one-byte caches is not supported)")
         if use_alibi:
             raise ValueError("QuantAttentionFused: use_alibi=True is not supported (the kernels rotate q and k, they add no ALiBi bias)")
         if attention_shapes is not None:
@@ -108,11 +171,15 @@ class QuantAttentionFused(nn.Module):
         self.sin = torch.cat((ang.sin(), ang.sin()), -1).half()
         self.per_sequence = bool(per_sequence)
         self.kv_cache_dtype, self.k_scale, self.v_scale = kv_cache_dtype, k_scale, v_scale
+        self.sliding_window = None if sliding_window is None else int(sliding_window)
+        self.prefill_chunk = int(prefill_chunk)
+        # rows per sequence and KV head: the whole context, or a ring bounded by the window (max_seq_len stays the position bound)
+        self.cache_rows = max_seq_len if sliding_window is None else ring_rows(sliding_window, prefill_chunk, max_seq_len)
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self._allocate(self.cache_batch_size, dev)
 
     def _allocate(self, batch, dev):
-        shape = (batch, self.n_kv_heads, self.max_seq_len, HEAD_DIM)
+        shape = (batch, self.n_kv_heads, self.cache_rows, HEAD_DIM)
         self.k_cache = torch.zeros(shape, dtype=KV_CACHE_DTYPES[self.kv_cache_dtype], device=dev)
         self.v_cache = torch.zeros(shape, dtype=KV_CACHE_DTYPES[self.kv_cache_dtype], device=dev)
         self.cache_batch_size = batch
@@ -172,7 +239,14 @@ class QuantAttentionFused(nn.Module):
         The module applies causal masking itself: ``attention_mask`` is accepted and IGNORED, as the reference's single-token path
         ignores it.  A batch size other than the cache's reallocates the caches and
         restarts at position 0, as the reference does.  ValueError where ``start_pos + T`` would exceed ``max_seq_len`` (the
-        reference rolls its cache; this module refuses).
+        reference rolls its cache and re-labels the cached keys; this module refuses at the last row of its RoPE tables -- with
+        ``sliding_window`` the caches are rings bounded by the window, and that is the only limit on the context).
+
+        ``sliding_window=W``: query at position p attends positions max(0, p - W + 1) .. p; all four paths run the windowed launches.
+        On a ring smaller than ``max_seq_len`` a forward takes at most ``prefill_chunk`` tokens (ValueError otherwise): feed a longer
+        prompt in chunks.  In ``per_sequence`` mode the padded rows of a chunk are written too and land behind the sequence's new
+        position, which in a wrapped ring are its OLDEST rows: the padding of a chunk counts toward T in W + T - 1 <= rows, and
+        ``prefill_chunk`` bounds T with its padding.
 
         Ragged batches need ``per_sequence=True``: ``new_tokens`` [B] says how many of the T rows of each sequence are real tokens
         (0 .. T, RIGHT-padded; None: T for all).  A list, a tuple or a CPU tensor is validated on the host (ValueError); a device int64
@@ -195,11 +269,17 @@ class QuantAttentionFused(nn.Module):
                              "the cache does not roll, call reset() or build the module with a larger max_seq_len"
                              + ("; a padded chunk needs room for its padding (all T rows of every sequence are written), and start_pos "
                                 "is an upper bound on the positions" if self.per_sequence else ""))
+        if self.sliding_window is not None and self.cache_rows < self.max_seq_len and T > self.prefill_chunk:
+            raise ValueError(f"QuantAttentionFused: {T} tokens in one forward on a ring of {self.cache_rows} rows (sliding_window = "
+                             f"{self.sliding_window}): feed the prompt in chunks of at most prefill_chunk = {self.prefill_chunk} tokens"
+                             + (" (padding included)" if self.per_sequence else ""))
         step, advance = self._new_tokens(new_tokens, B, T) if self.per_sequence else (None, T)
         if not hidden_states.is_cuda:
             raise RuntimeError("hidden_states must be a GPU tensor: the attention kernels have no CPU implementation")
         nh, nkv = self.n_heads, self.n_kv_heads
         ks = {} if self.kv_cache_dtype == "fp16" else dict(k_scale=self.k_scale, v_scale=self.v_scale)   # byte caches: the fp8 launches
+        if self.sliding_window is not None:                                                              # ring caches: the windowed launches
+            ks = dict(window=self.sliding_window, table_rows=self.max_seq_len)
         qkv = self.qkv_proj(hidden_states.reshape(B * T, self.hidden_size).contiguous())
         att = torch.empty((B * T, nh * HEAD_DIM), dtype=torch.float16, device=qkv.device)
         if self.per_sequence:

@@ -510,13 +510,41 @@ def _byte_caches(k_cache, v_cache):
     return kb
 
 
+def _window(window, table_rows, k_cache, v_cache, cos_table, who):
+    """The (window, ring_rows, table_rows) ints of a windowed launch (quick_*_win_f16): fp16 ring caches [B, nkv, ring_rows, D];
+    ``table_rows`` defaults to the rows of ``cos_table``.  Byte caches with a window are a ValueError (out of scope)."""
+    if k_cache.dtype in _BYTE_DTYPES or v_cache.dtype in _BYTE_DTYPES:
+        raise ValueError(f"{who}: a sliding window over one-byte (fp8) caches is not supported; use fp16 caches or window=None")
+    for t, name in ((k_cache, "k_cache"), (v_cache, "v_cache")):
+        _expect(t, torch.float16, name)
+        if t.dim() != 4 or not t.is_contiguous() or t.shape != k_cache.shape:
+            raise ValueError(f"{who}: {name} must be a contiguous ring cache [batch, n_kv_heads, ring_rows, head_dim] of k_cache's shape")
+    if table_rows is None:
+        if cos_table is None:
+            raise ValueError(f"{who}: window needs table_rows (the exclusive bound on positions; there is no RoPE table to take it from)")
+        table_rows = cos_table.shape[0]
+    return int(window), k_cache.shape[2], int(table_rows)
+
+
 def rope_kv_write(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, tokens, n_heads, n_kv_heads, head_dim, per_sequence=False,
-                  k_scale=1.0, v_scale=1.0):
+                  k_scale=1.0, v_scale=1.0, window=None, table_rows=None):
     """Prefill: qkv [B * T, (nh + 2 nkv) D] -> rotated q in q_out [B, nh, T, D], rotated k and v into the caches at
     positions *pos0 .. *pos0 + T - 1.  ``per_sequence``: pos0 is a device int64 [B] and sequence b starts at pos0[b]
     (quick_rope_kv_write_seq_f16); a sequence whose start lies outside 0 .. L - T is skipped.  One-byte caches
     (``torch.float8_e4m3fn``, or ``uint8`` holding the same bytes) are written by quick_rope_kv_write_fp8 as
-    ``attention.quantize_kv`` of the rows the fp16 launch would store, with ``k_scale`` / ``v_scale``; q_out is the same, bit for bit."""
+    ``attention.quantize_kv`` of the rows the fp16 launch would store, with ``k_scale`` / ``v_scale``; q_out is the same, bit for bit.
+    ``window`` (fp16 caches only): the caches are rings of ``k_cache.shape[2]`` rows and the token at position j is stored at row
+    j % ring_rows (quick_rope_kv_write_win_f16); ``table_rows`` bounds the positions (default: the rows of ``cos_table``)."""
+    if window is not None:
+        _, ring, table_rows = _window(window, table_rows, k_cache, v_cache, cos_table, "rope_kv_write")
+        if per_sequence:
+            _per_sequence_pos(pos0, qkv.shape[0] // tokens, k_cache, "pos0")
+        rc = _lib.load().quick_rope_kv_write_win_f16(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos0.data_ptr(),
+                                                     q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), qkv.shape[0] // tokens,
+                                                     tokens, n_heads, n_kv_heads, head_dim, ring, table_rows, int(per_sequence), _stream())
+        if rc != _OK:
+            _raise(rc)
+        return q_out
     if _byte_caches(k_cache, v_cache):
         if per_sequence:
             _per_sequence_pos(pos0, qkv.shape[0] // tokens, k_cache, "pos0")
@@ -544,14 +572,29 @@ def rope_kv_write(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, toke
     return q_out
 
 
-def prefill_attention(q, k_cache, v_cache, pos0, out, n_heads, n_kv_heads, head_dim, per_sequence=False, k_scale=1.0, v_scale=1.0):
+def prefill_attention(q, k_cache, v_cache, pos0, out, n_heads, n_kv_heads, head_dim, per_sequence=False, k_scale=1.0, v_scale=1.0,
+                      window=None, table_rows=None):
     """Causal attention of T new tokens over the cache (quick_prefill_attention_f16): q [B, nh, T, D] as rope_kv_write leaves it, caches
     [B, nkv, L, D] with rows *pos0 .. *pos0 + T - 1 written, pos0 a device int64 -> out [B * T, nh * D] (row b * T + t).  Query t attends
     cache rows 0 .. *pos0 + t; no host read, no mask tensor.  ``per_sequence``: pos0 is a device int64 [B] and query t of sequence b
     attends rows 0 .. pos0[b] + t (quick_prefill_attention_seq_f16); a sequence whose start lies outside 0 .. L - T is skipped.
-    One-byte caches run quick_prefill_attention_fp8 with ``k_scale`` / ``v_scale`` (see rope_kv_write)."""
+    One-byte caches run quick_prefill_attention_fp8 with ``k_scale`` / ``v_scale`` (see rope_kv_write).
+    ``window`` (fp16 ring caches, see rope_kv_write): query t attends positions max(0, pos0 + t - window + 1) .. pos0 + t
+    (quick_prefill_attention_win_f16).  ``table_rows``, the exclusive bound on positions, must be given with it; on a ring that can wrap
+    (ring_rows < table_rows) a chunk needs window + T - 1 <= ring_rows."""
     if per_sequence:
         _per_sequence_pos(pos0, q.shape[0], k_cache, "pos0")
+    if window is not None:
+        window, ring, table_rows = _window(window, table_rows, k_cache, v_cache, None, "prefill_attention")
+        for t, name in ((q, "q"), (out, "out")):
+            _expect(t, torch.float16, name)
+        _expect(pos0, torch.int64, "pos0")
+        rc = _lib.load().quick_prefill_attention_win_f16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), pos0.data_ptr(),
+                                                         out.data_ptr(), q.shape[0], q.shape[2], n_heads, n_kv_heads, head_dim, ring,
+                                                         window, table_rows, head_dim ** -0.5, int(per_sequence), _stream())
+        if rc != _OK:
+            _raise(rc)
+        return out
     if _byte_caches(k_cache, v_cache):
         for t, name in ((q, "q"), (out, "out")):
             _expect(t, torch.float16, name)
@@ -601,11 +644,24 @@ def decode_attention(q, k_cache, v_cache, pos, out, n_heads, n_kv_heads, head_di
 
 
 def rope_attention(qkv, cos_table, sin_table, pos, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, per_sequence=False,
-                   k_scale=1.0, v_scale=1.0):
+                   k_scale=1.0, v_scale=1.0, window=None, table_rows=None):
     """rope_kv_append + decode_attention in one launch: qkv [B, (nh + 2 nkv) D] -> out [B, nh * D].  ``per_sequence``: pos is a device
     int64 [B]; sequence b rotates with table row pos[b], appends at cache row pos[b] and attends rows 0 .. pos[b]
     (quick_decode_rope_attention_seq_f16); a sequence whose position lies outside 0 .. L - 1 is skipped.  One-byte caches run
-    quick_decode_rope_attention_fp8 with ``k_scale`` / ``v_scale``: the new token is appended as bytes and attended in that form."""
+    quick_decode_rope_attention_fp8 with ``k_scale`` / ``v_scale``: the new token is appended as bytes and attended in that form.
+    ``window`` (fp16 ring caches, see rope_kv_write): the token is appended at row pos % ring_rows and attends positions
+    max(0, pos - window + 1) .. pos (quick_decode_rope_attention_win_f16)."""
+    if window is not None:
+        window, ring, table_rows = _window(window, table_rows, k_cache, v_cache, cos_table, "rope_attention")
+        if per_sequence:
+            _per_sequence_pos(pos, qkv.shape[0], k_cache, "pos")
+        rc = _lib.load().quick_decode_rope_attention_win_f16(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos.data_ptr(),
+                                                             k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(), qkv.shape[0], n_heads,
+                                                             n_kv_heads, head_dim, ring, window, table_rows, head_dim ** -0.5,
+                                                             int(per_sequence), _stream())
+        if rc != _OK:
+            _raise(rc)
+        return out
     if _byte_caches(k_cache, v_cache):
         if per_sequence:
             _per_sequence_pos(pos, qkv.shape[0], k_cache, "pos")
@@ -641,6 +697,16 @@ def attention_describe(batch, n_heads, n_kv_heads, head_dim, cache_len, kv_cache
     buf = ctypes.create_string_buffer(128)
     fn = _lib.load().quick_decode_rope_attention_fp8_describe if kv_cache_dtype == "fp8_e4m3" else _lib.load().quick_decode_rope_attention_describe
     rc = fn(batch, n_heads, n_kv_heads, head_dim, cache_len, buf, len(buf))
+    if rc != _OK:
+        _raise(rc)
+    return buf.value.decode()
+
+
+def window_attention_describe(batch, tokens, n_heads, n_kv_heads, head_dim, ring_rows, window, table_rows):
+    """One line describing the windowed attention launch for this shape (quick_attention_win_describe; host-only): tokens == 1 the
+    decode launch, more tokens the prefill launch."""
+    buf = ctypes.create_string_buffer(160)
+    rc = _lib.load().quick_attention_win_describe(batch, tokens, n_heads, n_kv_heads, head_dim, ring_rows, window, table_rows, buf, len(buf))
     if rc != _OK:
         _raise(rc)
     return buf.value.decode()

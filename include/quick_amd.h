@@ -399,6 +399,61 @@ int quick_prefill_attention_win_f16(const void* q, const void* k_cache, const vo
  * kv_rows=32 waves=4 ...").  The same shape refusals as the launches. */
 int quick_attention_win_describe(int batch, int tokens, int n_heads, int n_kv_heads, int head_dim, int ring_rows, int window,
                                  int table_rows, char* text, size_t text_bytes);
+/*
+ * Attention over a PAGED KV cache, fp16 (opt-in; every entry point above is unchanged).  Cache memory is a pool of fixed-size pages and a
+ * block table per sequence, so a batch is charged for the tokens alive, not for batch * the longest context.
+ *   k_pool, v_pool  [num_pages, n_kv_heads, page_size, 128] fp16: a page holds page_size consecutive positions of ONE sequence, for all
+ *                   KV heads
+ *   P = page_size   32, 64, 128 or 256: whole multiples of the decode sweep's 16-row chunk and of the prefill kernel's 32-row tile, so
+ *                   a chunk or a tile never straddles a page and the table is read once per chunk or tile, wave-uniform
+ *   block_table     DEVICE int32 [batch, max_pages]: block_table[b][i] is the pool page of positions i P .. i P + P - 1 of sequence b;
+ *                   position j of sequence b, KV head h, lives at pool row (block_table[b][j / P], h, j % P)
+ *   table_rows      rows of the cos / sin tables; positions are bounded (exclusive) by min(table_rows, max_pages * P)
+ * Keys keep the RoPE of their absolute position; the rounding points are those of the linear launches, operation for operation: on the
+ * gathered linear cache the results are bit for bit those of quick_rope_kv_write_f16, of the grouped MFMA decode sweep
+ * (quick_decode_rope_attention_win_f16 with ring_rows = window = table_rows) and of quick_prefill_attention_f16.
+ * Never read.  Every request is clamped, as a logical position, to [0, last written position] before it is mapped: table columns behind
+ * the last written position's page and pool pages named by no needed column are never read and may hold anything (-1; NaN keys, +-Inf
+ * values).  The prefill launch never writes the pool; the decode launch writes this token's row and nothing else.
+ * A needed entry outside 0 .. num_pages - 1: a write (the write launch, the decode launch's append) drops that row; a read stays inside
+ * the pool (decode: the id is pulled inside; prefill: the tile is taken as zeros and nothing is requested).  No address ever leaves the
+ * pool and no other sequence's page is written, whatever the table holds; that sequence's output is unspecified.  The same page id may
+ * stand in several sequences' rows (a shared prefix); keeping writers apart is the caller's business.
+ * per_sequence, as in the window launches: 0 -- pos / pos0 is a DEVICE pointer to one int64 shared by the batch (a value outside the
+ * valid range is pulled inside); non-zero -- to int64 [batch], and a sequence whose position lies outside the valid range is skipped and
+ * left untouched: pool, q_out and out.  Valid: pos0 in 0 .. bound - tokens, *pos in 0 .. bound - 1, bound = min(table_rows, max_pages * P).
+ * Every entry point answers before any GPU work, with a sentence in quick_amd_last_error(), in this order:
+ *   a size <= 0 (batch, tokens, n_heads, n_kv_heads, num_pages, page_size, max_pages, table_rows)         QUICK_ERR_INVALID_ARGUMENT
+ *   page_size not 32, 64, 128 or 256; tokens > table_rows; max_pages * page_size < tokens                  QUICK_ERR_INVALID_ARGUMENT
+ *   head_dim != 128, n_heads % n_kv_heads != 0, decode: a group other than 1, 2, 4, 8                     QUICK_ERR_UNSUPPORTED
+ *   a grid limit (write: batch * tokens > 65535; attention: batch or n_heads > 65535)                     QUICK_ERR_UNSUPPORTED
+ *   a null pointer                                                                                        QUICK_ERR_INVALID_ARGUMENT
+ */
+/* quick_rope_kv_write_f16 into the pool: token t is rotated with table row pos0 + t and its K and V are stored at pool row
+ * (block_table[b][(pos0 + t) / P], kvh, (pos0 + t) % P).  q_out and the stored rows are bit for bit what quick_rope_kv_write_f16 writes
+ * (at row pos0 + t of a linear cache) for the same qkv and position. */
+int quick_rope_kv_write_paged_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos0, void* q_out, void* k_pool,
+                                  void* v_pool, const void* block_table, int batch, int tokens, int n_heads, int n_kv_heads, int head_dim,
+                                  int num_pages, int page_size, int max_pages, int table_rows, int per_sequence, void* hip_stream);
+/* One launch: RoPE at *pos, append at this token's page and row, single-query attention over positions 0 .. *pos; the new token comes
+ * from registers.  1, 2, 4 or 8 query heads per KV head, a KV head's whole group served from ONE sweep with the scores on
+ * v_mfma_f32_16x16x32_f16: one workgroup per (sequence, KV head), 16-row chunks per wave, one table read per chunk. */
+int quick_decode_rope_attention_paged_f16(const void* qkv, const void* cos_table, const void* sin_table, const void* pos, void* k_pool,
+                                          void* v_pool, void* out, const void* block_table, int batch, int n_heads, int n_kv_heads,
+                                          int head_dim, int num_pages, int page_size, int max_pages, int table_rows, float scale,
+                                          int per_sequence, void* hip_stream);
+/* quick_prefill_attention_f16 over the pool: query t attends positions 0 .. pos0 + t, whose rows quick_rope_kv_write_paged_f16 has
+ * written.  Tiling, LDS images, online softmax, rounding points and the way out are that kernel's; each 32-row tile is fetched through
+ * the table.  out: [batch * tokens, n_heads * 128]. */
+int quick_prefill_attention_paged_f16(const void* q, const void* k_pool, const void* v_pool, const void* pos0, void* out,
+                                      const void* block_table, int batch, int tokens, int n_heads, int n_kv_heads, int head_dim,
+                                      int num_pages, int page_size, int max_pages, int table_rows, float scale, int per_sequence,
+                                      void* hip_stream);
+/* The paged attention launch for this shape as one line (host-only): tokens == 1 describes the decode launch ("decode-paged-mfma heads=4
+ * waves=4 set_rows=64 page_size=64 max_pages=64 grid=8x16"), more tokens the prefill launch ("prefill-paged-mfma q_rows=64 kv_rows=32
+ * waves=4 page_size=64 max_pages=64 grid=2x32x16").  The same shape refusals as the launches. */
+int quick_attention_paged_describe(int batch, int tokens, int n_heads, int n_kv_heads, int head_dim, int num_pages, int page_size,
+                                   int max_pages, int table_rows, char* text, size_t text_bytes);
 int quick_silu_mul_f16(const void* gate_up, void* y, int rows, int intermediate, void* hip_stream);
 
 /* lm_head of a decode step with the greedy arg-max folded in (the reference: torch linear + max on the fp16 layer AWQ leaves

@@ -46,6 +46,10 @@ _SIGNATURES = {
     "quick_decode_rope_attention_win_f16": (_I, [_P] * 7 + [_I] * 7 + [ctypes.c_float, _I, _P]),
     "quick_prefill_attention_win_f16": (_I, [_P] * 5 + [_I] * 8 + [ctypes.c_float, _I, _P]),
     "quick_attention_win_describe": (_I, [_I] * 8 + [ctypes.c_char_p, _Z]),
+    "quick_rope_kv_write_paged_f16": (_I, [_P] * 8 + [_I] * 10 + [_P]),
+    "quick_decode_rope_attention_paged_f16": (_I, [_P] * 8 + [_I] * 8 + [ctypes.c_float, _I, _P]),
+    "quick_prefill_attention_paged_f16": (_I, [_P] * 6 + [_I] * 9 + [ctypes.c_float, _I, _P]),
+    "quick_attention_paged_describe": (_I, [_I] * 9 + [ctypes.c_char_p, _Z]),
     "quick_silu_mul_f16": (_I, [_P, _P, _I, _I, _P]),
     "quick_lm_head_workspace_bytes": (_Z, [_I]),
     "quick_lm_head_argmax_f16": (_I, [_P, _P, ctypes.c_float, _P, _P, _P, _P, _P, _Z, _I, _I, _I, _P]),

@@ -28,6 +28,12 @@ its own length.  ``start_pos`` is then a host-side UPPER BOUND on the largest po
 per cache: ``k_scale`` and ``v_scale``, host floats and constants of a captured graph.  ``quantize_kv`` / ``dequantize_kv`` below are the
 format, restated in torch: the kernels store ``quantize_kv`` of the fp16 rows the fp16 module would store and attend their
 ``dequantize_kv`` -- the new token of a decode step included, so step p attends what step p + 1 reads.
+
+``page_size=P, num_pages=N`` (opt-in; fp16, full attention) makes the cache PAGED: two pools ``[N, n_kv_heads, P, 128]`` and an int32
+block table ``[batch, ceil(max_seq_len / P)]`` in which ``block_table[b][i]`` names the pool page of positions i P .. i P + P - 1 of
+sequence b (-1: none).  A sequence holds ceil(length / P) pages, taken from a host-side ``PageAllocator`` as it grows and given back by
+``reset``: memory is charged for the tokens alive, not for batch * max_seq_len.  ``paged_slot`` / ``gather_pages`` / ``scatter_pages``
+restate the mapping in torch; the results are those of the linear module bit for bit.
 """
 import math
 import os
@@ -119,10 +125,77 @@ def window_attention_reference(q, k_ring, v_ring, pos0, window):
     return out.reshape(B * T, nh * Dh)
 
 
+PAGE_SIZES = (32, 64, 128, 256)
+
+
+def _check_page_size(page_size, who):
+    if page_size not in PAGE_SIZES or int(page_size) != page_size:
+        raise ValueError(f"{who}: page_size must be one of {PAGE_SIZES}, got {page_size!r}")
+    return int(page_size)
+
+
+def paged_slot(pos, block_table_row, page_size):
+    """(page, row) of position ``pos`` (an int, or an integer tensor of positions) of the sequence whose block table row is
+    ``block_table_row``: (block_table_row[pos // page_size], pos % page_size)."""
+    P = _check_page_size(page_size, "paged_slot")
+    col = pos // P
+    if isinstance(col, torch.Tensor):
+        return block_table_row[col.to(block_table_row.device)].long(), pos % P
+    return int(block_table_row[col]), pos % P
+
+
+def gather_pages(pool, block_table_row, length):
+    """Positions 0 .. length - 1 of one sequence out of a pool [num_pages, nkv, P, D], as a linear [nkv, length, D] tensor; no page
+    behind the last needed column of ``block_table_row`` is looked at."""
+    P = pool.shape[2]
+    pos = torch.arange(int(length), device=pool.device)
+    page, row = paged_slot(pos, block_table_row, P)
+    return pool[page, :, row].transpose(0, 1).contiguous()
+
+
+def scatter_pages(pool, block_table_row, linear):
+    """The inverse of gather_pages (for building fixtures): rows 0 .. length - 1 of ``linear`` [nkv, length, D] into their pool rows,
+    in place; every other pool row keeps what it holds.  Returns ``pool``."""
+    P = pool.shape[2]
+    pos = torch.arange(linear.shape[1], device=pool.device)
+    page, row = paged_slot(pos, block_table_row, P)
+    pool[page, :, row] = linear.transpose(0, 1).to(pool.dtype)
+    return pool
+
+
+class PageAllocator:
+    """A host-side free list over pages 0 .. num_pages - 1.  ``take(n)`` is all-or-nothing; ``give(pages)`` returns pages for reuse."""
+
+    def __init__(self, num_pages):
+        if int(num_pages) != num_pages or num_pages < 1:
+            raise ValueError(f"PageAllocator: num_pages must be a whole number >= 1, got {num_pages!r}")
+        self.num_pages = int(num_pages)
+        self._free = list(range(self.num_pages - 1, -1, -1))     # (a stack: page 0 goes out first, a page given back is reused first)
+
+    @property
+    def free(self):
+        return len(self._free)
+
+    def take(self, n):
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"PageAllocator: cannot take {n} pages")
+        if n > len(self._free):
+            raise RuntimeError(f"PageAllocator: out of pages: {len(self._free)} of {self.num_pages} are free, {n} were asked for")
+        return [self._free.pop() for _ in range(n)]
+
+    def give(self, pages):
+        pages = [int(p) for p in pages]
+        held = set(self._free)
+        if len(set(pages)) != len(pages) or any(p < 0 or p >= self.num_pages or p in held for p in pages):
+            raise ValueError(f"PageAllocator: give({pages}): pages must be distinct, inside 0 .. {self.num_pages - 1} and not free already")
+        self._free.extend(reversed(pages))
+
+
 class QuantAttentionFused(nn.Module):
     def __init__(self, hidden_size, n_heads, n_kv_heads, qkv_layer, o_proj, dev, max_seq_len, use_alibi=False, attention_shapes=None,
                  rope_theta=10000, per_sequence=False, kv_cache_dtype="fp16", k_scale=1.0, v_scale=1.0, sliding_window=None,
-                 prefill_chunk=512):
+                 prefill_chunk=512, page_size=None, num_pages=None):
         super().__init__()
         _, k_scale, v_scale = _check_kv_cache("QuantAttentionFused", kv_cache_dtype, k_scale, v_scale)
         if prefill_chunk is None or int(prefill_chunk) != prefill_chunk or prefill_chunk < 1:
@@ -132,6 +205,16 @@ class QuantAttentionFused(nn.Module):
                 raise ValueError(f"QuantAttentionFused: sliding_window must be a whole number >= 1 (or None), got {sliding_window!r}")
             if kv_cache_dtype != "fp16":
                 raise ValueError("QuantAttentionFused: sliding_window needs kv_cache_dtype='fp16' (a window over one-byte caches is not supported)")
+        if page_size is not None:
+            page_size = _check_page_size(page_size, "QuantAttentionFused")
+            if sliding_window is not None:
+                raise ValueError("QuantAttentionFused: page_size with sliding_window is not supported (a windowed paged cache is out of scope)")
+            if kv_cache_dtype != "fp16":
+                raise ValueError("QuantAttentionFused: page_size needs kv_cache_dtype='fp16' (a paged one-byte cache is out of scope)")
+            if num_pages is None or int(num_pages) != num_pages or num_pages < 1:
+                raise ValueError(f"QuantAttentionFused: page_size needs num_pages, a whole number >= 1, got {num_pages!r}")
+        elif num_pages is not None:
+            raise ValueError("QuantAttentionFused: num_pages needs page_size")
         if use_alibi:
             raise ValueError("QuantAttentionFused: use_alibi=True is not supported (the kernels rotate q and k, they add no ALiBi bias)")
         if attention_shapes is not None:
@@ -175,11 +258,22 @@ class QuantAttentionFused(nn.Module):
         self.prefill_chunk = int(prefill_chunk)
         # rows per sequence and KV head: the whole context, or a ring bounded by the window (max_seq_len stays the position bound)
         self.cache_rows = max_seq_len if sliding_window is None else ring_rows(sliding_window, prefill_chunk, max_seq_len)
+        # paged: the pools stand in k_cache / v_cache ([num_pages, nkv, P, D]); the block table, the allocator and the bounds come with them
+        self.page_size = page_size
+        self.num_pages = None if page_size is None else int(num_pages)
         self.pos = torch.zeros(1, dtype=torch.int64, device=dev)
         self._allocate(self.cache_batch_size, dev)
 
     def _allocate(self, batch, dev):
         shape = (batch, self.n_kv_heads, self.cache_rows, HEAD_DIM)
+        if self.page_size is not None:
+            shape = (self.num_pages, self.n_kv_heads, self.page_size, HEAD_DIM)
+            self.max_pages = -(-self.max_seq_len // self.page_size)
+            self._table_host = torch.full((batch, self.max_pages), -1, dtype=torch.int32)
+            self.block_table = self._table_host.to(dev)
+            self.allocator = PageAllocator(self.num_pages)
+            self._pages = [[] for _ in range(batch)]             # the pages of every sequence, in position order
+            self._len_bound = [0] * batch                        # host-side upper bound of every sequence's length
         self.k_cache = torch.zeros(shape, dtype=KV_CACHE_DTYPES[self.kv_cache_dtype], device=dev)
         self.v_cache = torch.zeros(shape, dtype=KV_CACHE_DTYPES[self.kv_cache_dtype], device=dev)
         self.cache_batch_size = batch
@@ -195,7 +289,69 @@ class QuantAttentionFused(nn.Module):
             else:
                 setattr(self, name, fn(t).half())
         self.pos = fn(self.pos).to(torch.int64)
+        if self.page_size is not None:
+            self.block_table = fn(self.block_table).to(torch.int32)
         return self
+
+    # ------------------------------------------------------------------------------------------ paged cache: host-side bookkeeping
+    @property
+    def k_pool(self):
+        return self.k_cache
+
+    @property
+    def v_pool(self):
+        return self.v_cache
+
+    @property
+    def free_pages(self):
+        """Pages of the pool no sequence holds."""
+        self._need_pages("free_pages")
+        return self.allocator.free
+
+    def _need_pages(self, what):
+        if self.page_size is None:
+            raise ValueError(f"QuantAttentionFused: {what} needs a paged cache (page_size=...)")
+
+    @staticmethod
+    def _capturing():
+        return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+    def _push_table(self):
+        self.block_table.copy_(self._table_host)                 # in place, at the same address: a captured graph reads the new table
+
+    def reserve(self, lengths):
+        """Make sure sequence b holds the pages of positions 0 .. lengths[b] - 1 (an int: every sequence) -- what ``forward`` does for the
+        tokens it is given, done ahead of time: a captured step allocates nothing, so call this before the capture and between replays.
+        All or nothing: RuntimeError when the pool has too few free pages, and then nothing has changed.  Never gives pages back."""
+        self._need_pages("reserve")
+        B = self.cache_batch_size
+        lengths = [int(lengths)] * B if not isinstance(lengths, (list, tuple, torch.Tensor)) else [int(n) for n in lengths]
+        if len(lengths) != B or any(n < 0 or n > self.max_seq_len for n in lengths):
+            raise ValueError(f"QuantAttentionFused: reserve: one length in 0 .. max_seq_len = {self.max_seq_len} per sequence ({B}), got {lengths}")
+        need = [max(0, -(-n // self.page_size) - len(held)) for n, held in zip(lengths, self._pages)]
+        if not any(need):
+            return
+        if self._capturing():
+            raise RuntimeError(f"QuantAttentionFused: {sum(need)} pages are missing while a stream is capturing, and a captured step "
+                               "allocates nothing: call reserve(lengths) before the capture (and between replays)")
+        try:
+            got = self.allocator.take(sum(need))
+        except RuntimeError as e:
+            raise RuntimeError(f"QuantAttentionFused: the page pool is exhausted ({e}); free slots with reset(slots=...) or build the "
+                               "module with more num_pages") from None
+        for b, n in enumerate(need):
+            mine, got = got[:n], got[n:]
+            self._table_host[b, len(self._pages[b]):len(self._pages[b]) + n] = torch.tensor(mine, dtype=torch.int32)
+            self._pages[b] += mine
+        self._push_table()
+
+    def _release(self, slots):
+        for b in slots:
+            self.allocator.give(self._pages[b])
+            self._pages[b] = []
+            self._len_bound[b] = 0
+            self._table_host[b] = -1
+        self._push_table()
 
     def reset(self, slots=None):
         """Back to position 0 (the cache rows are overwritten as the positions are).  ``slots`` (``per_sequence=True`` only): the indices
@@ -204,6 +360,8 @@ class QuantAttentionFused(nn.Module):
         if slots is None:
             self.start_pos = 0
             self.pos.zero_()
+            if self.page_size is not None:                      # every page goes back, every table row to -1
+                self._release(range(self.cache_batch_size))
             return
         if not self.per_sequence:
             raise ValueError("QuantAttentionFused: reset(slots=...) needs per_sequence=True (this module keeps one position for the batch)")
@@ -212,6 +370,9 @@ class QuantAttentionFused(nn.Module):
             raise ValueError(f"QuantAttentionFused: reset(slots={slots}): slots are 0 .. {self.cache_batch_size - 1}")
         if slots:
             self.pos[torch.tensor(slots, dtype=torch.int64, device=self.pos.device)] = 0
+        if self.page_size is not None:                          # (the host read below makes the other slots' bounds exact again)
+            self._release(sorted(set(slots)))
+            self._len_bound = [int(p) for p in self.pos.tolist()]
         self.start_pos = int(self.pos.max())
 
     def _new_tokens(self, new_tokens, B, T):
@@ -280,6 +441,13 @@ class QuantAttentionFused(nn.Module):
         ks = {} if self.kv_cache_dtype == "fp16" else dict(k_scale=self.k_scale, v_scale=self.v_scale)   # byte caches: the fp8 launches
         if self.sliding_window is not None:                                                              # ring caches: the windowed launches
             ks = dict(window=self.sliding_window, table_rows=self.max_seq_len)
+        if self.page_size is not None:                                                                   # page pools: the paged launches
+            # the pages of every sequence's bound plus its new tokens, before any launch; exact where the counts are host integers
+            counts = [T] * B if step is None or step.is_cuda else step.tolist()
+            grown = [min(n + c, self.max_seq_len) for n, c in zip(self._len_bound, counts)]
+            self.reserve(grown)
+            self._len_bound = grown
+            ks = dict(block_table=self.block_table, page_size=self.page_size, table_rows=self.max_seq_len)
         qkv = self.qkv_proj(hidden_states.reshape(B * T, self.hidden_size).contiguous())
         att = torch.empty((B * T, nh * HEAD_DIM), dtype=torch.float16, device=qkv.device)
         if self.per_sequence:

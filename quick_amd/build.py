@@ -29,7 +29,7 @@ LIB = os.path.join(LIBDIR, "libquick_amd.so")
 TOOLS_DIR = os.path.join(os.path.dirname(PKG), "tools", "bin")   # measurement builds live with the tools, not with the product
 TOOLS_LIB = os.path.join(TOOLS_DIR, "libquick_amd_tools.so")
 FORCEZERO_LIB = os.path.join(LIBDIR, "libquick_amd_forcezero.so")
-SOURCES = ["w4a16_gemm.hip", "w4a16_skinny.hip", "w4a16_tiled.hip", "w4a16_wide.hip", "w4a16_plan.hip", "w4a16_xk.hip", "w4a16_xw.hip", "w4a16_xm.hip", "w4a16_lean.hip", "w4a16_lean_a.hip", "w4a16_lean_b.hip", "w4a16_lean_c.hip", "repack.hip", "decode_ops.hip", "prefill_attention.hip", "prefill_attention_seq.hip", "kv_fp8.hip", "attention_window.hip"]
+SOURCES = ["w4a16_gemm.hip", "w4a16_skinny.hip", "w4a16_tiled.hip", "w4a16_wide.hip", "w4a16_plan.hip", "w4a16_xk.hip", "w4a16_xw.hip", "w4a16_xm.hip", "w4a16_lean.hip", "w4a16_lean_a.hip", "w4a16_lean_b.hip", "w4a16_lean_c.hip", "repack.hip", "decode_ops.hip", "prefill_attention.hip", "prefill_attention_seq.hip", "kv_fp8.hip", "attention_window.hip", "attention_paged.hip"]
 HEADERS = ["w4a16_common.hpp", "prefill_attention.hpp", "w4a16_args.hpp", "w4a16_launch.hpp", "w4a16_plan.hpp", "w4a16_wide.hpp", "w4a16_xk.hpp", "w4a16_xk_host.hpp", "w4a16_xw.hpp", "w4a16_xw_host.hpp", "w4a16_xw_loop.inc", "w4a16_xws_loop.inc", "w4a16_xm.hpp", "w4a16_xm_host.hpp", "w4a16_xm_loop.inc", "w4a16_lean.hpp", "w4a16_lean_host.hpp", "w4a16_lean_inst.hpp", "gate_up_mi355x.hpp",
            os.path.join("..", "..", "include", "quick_amd.h")]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc"]

@@ -526,15 +526,61 @@ def _window(window, table_rows, k_cache, v_cache, cos_table, who):
     return int(window), k_cache.shape[2], int(table_rows)
 
 
+def _paged(block_table, page_size, table_rows, k_pool, v_pool, cos_table, batch, window, k_scale, v_scale, who):
+    """The (num_pages, page_size, max_pages, table_rows) ints of a paged launch (quick_*_paged_f16): fp16 pools
+    [num_pages, n_kv_heads, page_size, head_dim] and a device int32 block table [batch, max_pages]; ``table_rows`` defaults to the rows of
+    ``cos_table``.  Combined with a window, one-byte caches or fp8 scales: a ValueError (out of scope)."""
+    if window is not None:
+        raise ValueError(f"{who}: block_table and window together are not supported (a windowed paged cache is out of scope)")
+    if k_pool.dtype in _BYTE_DTYPES or v_pool.dtype in _BYTE_DTYPES:
+        raise ValueError(f"{who}: a block_table over one-byte (fp8) pools is not supported; use fp16 pools")
+    if k_scale != 1.0 or v_scale != 1.0:
+        raise ValueError(f"{who}: k_scale / v_scale belong to one-byte caches and cannot be combined with block_table")
+    if page_size is None:
+        raise ValueError(f"{who}: block_table needs page_size")
+    for t, name in ((k_pool, "k_cache"), (v_pool, "v_cache")):
+        if t.dim() != 4 or not t.is_contiguous() or t.shape != k_pool.shape or t.shape[2] != int(page_size):
+            raise ValueError(f"{who}: {name} must be a contiguous pool [num_pages, n_kv_heads, page_size = {page_size}, head_dim] of "
+                             f"k_cache's shape, got {list(t.shape)}")
+    if not isinstance(block_table, torch.Tensor) or block_table.dtype != torch.int32 or block_table.dim() != 2 \
+            or block_table.shape[0] != batch or not block_table.is_contiguous():
+        raise ValueError(f"{who}: block_table must be a contiguous int32 tensor [batch = {batch}, max_pages]")
+    if not block_table.is_cuda or block_table.device != k_pool.device:
+        raise ValueError(f"{who}: block_table must be a GPU tensor on the device of the pools ({k_pool.device}), it is on {block_table.device}")
+    if table_rows is None:
+        if cos_table is None:
+            raise ValueError(f"{who}: block_table needs table_rows (the exclusive bound on positions; there is no RoPE table to take it from)")
+        table_rows = cos_table.shape[0]
+    for t, name in ((k_pool, "k_cache"), (v_pool, "v_cache")):
+        _expect(t, torch.float16, name)
+    return k_pool.shape[0], int(page_size), block_table.shape[1], int(table_rows)
+
+
 def rope_kv_write(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, tokens, n_heads, n_kv_heads, head_dim, per_sequence=False,
-                  k_scale=1.0, v_scale=1.0, window=None, table_rows=None):
+                  k_scale=1.0, v_scale=1.0, window=None, table_rows=None, block_table=None, page_size=None):
     """Prefill: qkv [B * T, (nh + 2 nkv) D] -> rotated q in q_out [B, nh, T, D], rotated k and v into the caches at
     positions *pos0 .. *pos0 + T - 1.  ``per_sequence``: pos0 is a device int64 [B] and sequence b starts at pos0[b]
     (quick_rope_kv_write_seq_f16); a sequence whose start lies outside 0 .. L - T is skipped.  One-byte caches
     (``torch.float8_e4m3fn``, or ``uint8`` holding the same bytes) are written by quick_rope_kv_write_fp8 as
     ``attention.quantize_kv`` of the rows the fp16 launch would store, with ``k_scale`` / ``v_scale``; q_out is the same, bit for bit.
     ``window`` (fp16 caches only): the caches are rings of ``k_cache.shape[2]`` rows and the token at position j is stored at row
-    j % ring_rows (quick_rope_kv_write_win_f16); ``table_rows`` bounds the positions (default: the rows of ``cos_table``)."""
+    j % ring_rows (quick_rope_kv_write_win_f16); ``table_rows`` bounds the positions (default: the rows of ``cos_table``).
+    ``block_table`` (device int32 [B, max_pages], with ``page_size``; fp16 only): the caches are page pools
+    [num_pages, nkv, page_size, D] and the token at position j of sequence b is stored at pool row
+    (block_table[b][j // page_size], kvh, j % page_size) (quick_rope_kv_write_paged_f16); a row whose entry names no page is dropped."""
+    if block_table is not None:
+        B = qkv.shape[0] // tokens
+        pages, psize, max_pages, table_rows = _paged(block_table, page_size, table_rows, k_cache, v_cache, cos_table, B, window, k_scale,
+                                                     v_scale, "rope_kv_write")
+        if per_sequence:
+            _per_sequence_pos(pos0, B, k_cache, "pos0")
+        rc = _lib.load().quick_rope_kv_write_paged_f16(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos0.data_ptr(),
+                                                       q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), block_table.data_ptr(), B,
+                                                       tokens, n_heads, n_kv_heads, head_dim, pages, psize, max_pages, table_rows,
+                                                       int(per_sequence), _stream())
+        if rc != _OK:
+            _raise(rc)
+        return q_out
     if window is not None:
         _, ring, table_rows = _window(window, table_rows, k_cache, v_cache, cos_table, "rope_kv_write")
         if per_sequence:
@@ -573,7 +619,7 @@ def rope_kv_write(qkv, cos_table, sin_table, pos0, q_out, k_cache, v_cache, toke
 
 
 def prefill_attention(q, k_cache, v_cache, pos0, out, n_heads, n_kv_heads, head_dim, per_sequence=False, k_scale=1.0, v_scale=1.0,
-                      window=None, table_rows=None):
+                      window=None, table_rows=None, block_table=None, page_size=None):
     """Causal attention of T new tokens over the cache (quick_prefill_attention_f16): q [B, nh, T, D] as rope_kv_write leaves it, caches
     [B, nkv, L, D] with rows *pos0 .. *pos0 + T - 1 written, pos0 a device int64 -> out [B * T, nh * D] (row b * T + t).  Query t attends
     cache rows 0 .. *pos0 + t; no host read, no mask tensor.  ``per_sequence``: pos0 is a device int64 [B] and query t of sequence b
@@ -581,9 +627,24 @@ def prefill_attention(q, k_cache, v_cache, pos0, out, n_heads, n_kv_heads, head_
     One-byte caches run quick_prefill_attention_fp8 with ``k_scale`` / ``v_scale`` (see rope_kv_write).
     ``window`` (fp16 ring caches, see rope_kv_write): query t attends positions max(0, pos0 + t - window + 1) .. pos0 + t
     (quick_prefill_attention_win_f16).  ``table_rows``, the exclusive bound on positions, must be given with it; on a ring that can wrap
-    (ring_rows < table_rows) a chunk needs window + T - 1 <= ring_rows."""
+    (ring_rows < table_rows) a chunk needs window + T - 1 <= ring_rows.
+    ``block_table`` (with ``page_size`` and ``table_rows``; fp16 page pools, see rope_kv_write): query t attends positions
+    0 .. pos0 + t, each 32-row tile fetched through the table (quick_prefill_attention_paged_f16); the pool is never written."""
     if per_sequence:
         _per_sequence_pos(pos0, q.shape[0], k_cache, "pos0")
+    if block_table is not None:
+        pages, psize, max_pages, table_rows = _paged(block_table, page_size, table_rows, k_cache, v_cache, None, q.shape[0], window,
+                                                     k_scale, v_scale, "prefill_attention")
+        for t, name in ((q, "q"), (out, "out")):
+            _expect(t, torch.float16, name)
+        _expect(pos0, torch.int64, "pos0")
+        rc = _lib.load().quick_prefill_attention_paged_f16(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), pos0.data_ptr(),
+                                                           out.data_ptr(), block_table.data_ptr(), q.shape[0], q.shape[2], n_heads,
+                                                           n_kv_heads, head_dim, pages, psize, max_pages, table_rows, head_dim ** -0.5,
+                                                           int(per_sequence), _stream())
+        if rc != _OK:
+            _raise(rc)
+        return out
     if window is not None:
         window, ring, table_rows = _window(window, table_rows, k_cache, v_cache, None, "prefill_attention")
         for t, name in ((q, "q"), (out, "out")):
@@ -644,13 +705,27 @@ def decode_attention(q, k_cache, v_cache, pos, out, n_heads, n_kv_heads, head_di
 
 
 def rope_attention(qkv, cos_table, sin_table, pos, k_cache, v_cache, out, n_heads, n_kv_heads, head_dim, per_sequence=False,
-                   k_scale=1.0, v_scale=1.0, window=None, table_rows=None):
+                   k_scale=1.0, v_scale=1.0, window=None, table_rows=None, block_table=None, page_size=None):
     """rope_kv_append + decode_attention in one launch: qkv [B, (nh + 2 nkv) D] -> out [B, nh * D].  ``per_sequence``: pos is a device
     int64 [B]; sequence b rotates with table row pos[b], appends at cache row pos[b] and attends rows 0 .. pos[b]
     (quick_decode_rope_attention_seq_f16); a sequence whose position lies outside 0 .. L - 1 is skipped.  One-byte caches run
     quick_decode_rope_attention_fp8 with ``k_scale`` / ``v_scale``: the new token is appended as bytes and attended in that form.
     ``window`` (fp16 ring caches, see rope_kv_write): the token is appended at row pos % ring_rows and attends positions
-    max(0, pos - window + 1) .. pos (quick_decode_rope_attention_win_f16)."""
+    max(0, pos - window + 1) .. pos (quick_decode_rope_attention_win_f16).
+    ``block_table`` (with ``page_size``; fp16 page pools, see rope_kv_write): the token is appended at its page and row and attends
+    positions 0 .. pos, one table read per 16-row chunk (quick_decode_rope_attention_paged_f16)."""
+    if block_table is not None:
+        pages, psize, max_pages, table_rows = _paged(block_table, page_size, table_rows, k_cache, v_cache, cos_table, qkv.shape[0], window,
+                                                     k_scale, v_scale, "rope_attention")
+        if per_sequence:
+            _per_sequence_pos(pos, qkv.shape[0], k_cache, "pos")
+        rc = _lib.load().quick_decode_rope_attention_paged_f16(qkv.data_ptr(), cos_table.data_ptr(), sin_table.data_ptr(), pos.data_ptr(),
+                                                               k_cache.data_ptr(), v_cache.data_ptr(), out.data_ptr(),
+                                                               block_table.data_ptr(), qkv.shape[0], n_heads, n_kv_heads, head_dim, pages,
+                                                               psize, max_pages, table_rows, head_dim ** -0.5, int(per_sequence), _stream())
+        if rc != _OK:
+            _raise(rc)
+        return out
     if window is not None:
         window, ring, table_rows = _window(window, table_rows, k_cache, v_cache, cos_table, "rope_attention")
         if per_sequence:
@@ -707,6 +782,17 @@ def window_attention_describe(batch, tokens, n_heads, n_kv_heads, head_dim, ring
     decode launch, more tokens the prefill launch."""
     buf = ctypes.create_string_buffer(160)
     rc = _lib.load().quick_attention_win_describe(batch, tokens, n_heads, n_kv_heads, head_dim, ring_rows, window, table_rows, buf, len(buf))
+    if rc != _OK:
+        _raise(rc)
+    return buf.value.decode()
+
+
+def paged_attention_describe(batch, tokens, n_heads, n_kv_heads, head_dim, num_pages, page_size, max_pages, table_rows):
+    """One line describing the paged attention launch for this shape (quick_attention_paged_describe; host-only): tokens == 1 the
+    decode launch, more tokens the prefill launch."""
+    buf = ctypes.create_string_buffer(160)
+    rc = _lib.load().quick_attention_paged_describe(batch, tokens, n_heads, n_kv_heads, head_dim, num_pages, page_size, max_pages,
+                                                    table_rows, buf, len(buf))
     if rc != _OK:
         _raise(rc)
     return buf.value.decode()
